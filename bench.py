@@ -157,6 +157,28 @@ def issue_profile(eng, run_step, n, replay=True, one_stream=False):
             "drain_ms": round(1e3 * (t_end - ts[-1]), 3), "wall_ms_per_step": round(1e3 * (t_end - ts[0]) / n, 4)}
 
 
+DUMP_SAMPLE = 1 << 22        # floats per sampled buffer (16 MB)
+
+
+def dump_outputs(eng, losses, out_dir):
+    """What the last timed step hands its caller, as f32 .npy files: the loss vector train_step returns
+    ([g_total, g_adv, g_l1, g_hist, d_total, d_real, d_fake], or the indexed model's) and the weights and Adam moments
+    that step left in the flat buffers of both networks (engine.ParamStore memory order).  A buffer larger than
+    DUMP_SAMPLE floats is sampled at fixed positions (sorted, seed 0), the same for every run of the same arguments.
+    Every rank holds the same weights after the all-reduce: rank 0 writes."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": losses}
+    for net, store in (("g", eng.G), ("d", eng.D)):
+        for part in ("params", "m", "v"):
+            buf = getattr(store, part)
+            if buf.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(buf.numel(), DUMP_SAMPLE, replace=False))
+                buf = buf[torch.as_tensor(idx, device=buf.device)]
+            arrays[f"{net}_{part}"] = buf
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _host_info():
     info = {"cpus": os.cpu_count()}
     try:
@@ -189,6 +211,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one captured hipGraph (N=1 only). Measured "
                     "slower than eager two-stream launching on ROCm 7.2 (the replay serialises the weight-gradient branch), so off by default")
     ap.add_argument("--detail", default=None, help="write a per-call (entry point, shape) device-time table to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step "
+                    "computed (its losses and the updated weights, see dump_outputs) to DIR/<name>.npy")
     # RCCL tuning for the gradient all-reduce (N > 1).  xGMI is point-to-point, 7 links x ~153 GB/s per GPU: a single ring moves
     # 2 x 7/8 x 117 MB over one link direction (>= 1.34 ms); more channels light more links.  Unset = RCCL's
     # own choice.  No N > 1 measurement exists from this build's one-GPU boxes: the knobs are here for the 8-GPU node.
@@ -197,6 +221,8 @@ def main():
     ap.add_argument("--rccl-proto", default=None, help="NCCL_PROTO (Simple | LL | LL128)")
     ap.add_argument("--bucket-mb", type=float, default=None, help="minimum size of a gradient bucket (default 16 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.rccl_channels:
         os.environ["NCCL_MIN_NCHANNELS"] = os.environ["NCCL_MAX_NCHANNELS"] = str(args.rccl_channels)
     if args.rccl_algo:
@@ -276,6 +302,8 @@ def main():
         elapsed = comm.max_scalar(elapsed)
     ms_per_step = elapsed / args.steps * 1e3
     value = B * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:      # before the profiles below, which run further steps on the same weights
+        dump_outputs(eng, losses, args.dump_outputs)
 
     result = {
         "metric": "train images/sec (64x64x4 sprites)" if S == 64 else f"train images/sec ({S}x{S}x4 sprites)",

@@ -26,14 +26,17 @@ def test_png_decoder_all_filter_types_and_errors(tmp_path):
         png.decode_png(bytes(bad))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/datasets/rpg-maker-xp"), reason="reference dataset not on this machine")
-def test_png_decoder_equals_pil_on_the_reference_sprites():
+def test_png_decoder_equals_pil_on_the_reference_sprites(tmp_path):
+    """every third of the reference's 1176 rpg-maker-xp sprites, stored byte for byte (tests/golden/make_sprites.py)"""
     Image = pytest.importorskip("PIL.Image")
-    import glob
-    files = sorted(glob.glob("/root/reference/datasets/rpg-maker-xp/*/*/*.png"))
-    assert len(files) == 1176
-    for f in files[::3]:
-        assert (png.read_png(f) == np.asarray(Image.open(f).convert("RGBA"))).all(), f
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_sprites.npz"))
+    names, offsets, data = z["names"], z["offsets"], z["data"]
+    assert len(names) == 392 and len(offsets) == 393 and offsets[-1] == data.size
+    for i, name in enumerate(names):
+        f = str(tmp_path / f"{i}.png")
+        with open(f, "wb") as fh:
+            fh.write(data[offsets[i]:offsets[i + 1]].tobytes())
+        assert (png.read_png(f) == np.asarray(Image.open(f).convert("RGBA"))).all(), name
 
 
 def test_oracle_known_answers():
