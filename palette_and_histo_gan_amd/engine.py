@@ -1078,7 +1078,8 @@ class Pix2PixEngine:
         st = torch.cuda.current_stream()
         return (kind, B, self.side.enabled, self.side.stop_event_forks, self.side_hist.enabled, self.fuse_adam, self.use_head_fused, self.hist_fwd3, self.hist_bwd3,
                 self.hist_points, self.fuse_act_bwd, self.split_prep, self.full_pixels, self.use_conv_fewout, self.use_conv_strip, self.use_conv_fewin,
-                self.use_mfma, int(self.splitk_target), int(self.wgemm_want), int(self.wgemm_want_pipe), int(st.cuda_stream), int(st.stream_id),
+                self.use_mfma, bool(self.batch_invariant), bool(self.wgemm_pipe), int(self.splitk_target), int(self.wgemm_want), int(self.wgemm_want_pipe),
+                int(st.cuda_stream), int(st.stream_id),
                 None if dp is None else id(dp)) + extra
 
     def _bind_batch(self, src_t, real_t):
