@@ -331,6 +331,21 @@ int p2p_rgbuv_hist_hellinger_bwd3(int dtype, int N, int H, int W, const p2p_tens
                                   const float* hist_pred, const float* tot_true, const float* tot_pred, const float* sq_sum,
                                   float coef, float* gh_ws, float* dimg, void* stream);
 
+/* Backward of the standalone histogram (histogram.calculate_rgbuv_histogram under torch autograd), in two steps.
+ * 1. The normalisation and transpose: raw[N][3][size][size] as the forward kernels write it, grad_out = dL/d(normalised
+ *    histogram) in the reference's [N][size][size][3] layout, size 2..128; with T_n = sum raw_n and Hn = raw / T:
+ *    gh[n][c][i][j] = (grad_out[n][i][j][c] - sum_{c,i,j} grad_out[n] * Hn[n]) / T_n   (one workgroup per image, fixed order). */
+int p2p_hist_normalize_bwd(const float* raw, const float* grad_out, int N, int size, float* gh, void* stream);
+/* 2. d(sum gh * raw)/d(img) for an ARBITRARY raw-histogram gradient gh[N][3][64][64] at the reference's arguments (64 bins,
+ *    inverse-quadratic, sigma 0.02): the kernel of p2p_rgbuv_hist_hellinger_bwd3 without its Hellinger prep.  Writes ONE f32
+ *    slab dimg[N*H*W][4] (alpha gradient 0), 16-byte aligned. */
+int p2p_rgbuv_hist_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, const float* gh, float* dimg, void* stream);
+/*    The same for p2p_rgbuv_hist_general's arguments (size 2..128, method 0..2, sigma > 0; same codes): gh[N][3][size][size],
+ *    dimg[N*H*W][4] f32, the three components summed in the kernel.  Deterministic: every pixel is reduced by a fixed set of
+ *    lanes in a fixed order (no float atomics).  f32 vector arithmetic, for evaluation code. */
+int p2p_rgbuv_hist_general_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, int size, int method, float sigma,
+                               const float* gh, float* dimg, void* stream);
+
 /* ---- palette-index head (pix2pix_model.py:261-325) ------------------------------------------------------------ */
 
 /* z: logits view [N][H][W][C]; target: view holding the real palette index of every pixel (as a value of `dtype`).

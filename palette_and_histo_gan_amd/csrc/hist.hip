@@ -979,6 +979,22 @@ extern "C" int p2p_hellinger_finish(const float* sq_sum, float inv_global_batch,
     return p2p_check_launch("p2p_hellinger_finish");
 }
 
+// rgbuv_hist_bwd3_kernel from a raw-histogram gradient gh[N][3][64][64] to one f32 slab dimg[N*H*W][4]; shared by the fused
+// Hellinger backward and the standalone one (p2p_rgbuv_hist_bwd)
+static int launch_hist_bwd3(int dtype, int N, int H, int W, const p2p_tensor* img, const float* gh, float* dimg, hipStream_t st,
+                            const char* what) {
+    int nsplit = 1;
+    while (N * nsplit < 256 && (H * W) / (nsplit * 2) >= 8 * B3_PB) nsplit *= 2;       // one 12-wave workgroup per CU
+    constexpr int SHM = B3_SHM;
+    static_assert(SHM <= 160 * 1024, "rgbuv_hist_bwd3_kernel: LDS");
+    static bool attr = false;
+    if (!attr)
+        attr = (int)p2p_allow_lds((const void*)rgbuv_hist_bwd3_kernel<float>, SHM, "rgbuv_hist_bwd3_kernel<float>") &
+               (int)p2p_allow_lds((const void*)rgbuv_hist_bwd3_kernel<bf16_t>, SHM, "rgbuv_hist_bwd3_kernel<bf16>");
+    P2P_DISPATCH_DTYPE(dtype, (rgbuv_hist_bwd3_kernel<T><<<dim3(N, nsplit), B3_NT, SHM, st>>>(H, W, make_view(img), gh, dimg, nsplit)));
+    return p2p_check_launch(what);
+}
+
 extern "C" int p2p_rgbuv_hist_hellinger_bwd3(int dtype, int N, int H, int W, const p2p_tensor* fake, const float* hist_true,
                                              const float* hist_pred, const float* tot_true, const float* tot_pred,
                                              const float* sq_sum, float coef, float* gh_ws, float* dimg, void* stream) {
@@ -988,16 +1004,202 @@ extern "C" int p2p_rgbuv_hist_hellinger_bwd3(int dtype, int N, int H, int W, con
     hist_grad_prep_kernel<<<dim3(N), 256, 0, st>>>(hist_true, hist_pred, tot_true, tot_pred, sq_sum, coef, gh_ws);
     int rc = p2p_check_launch("p2p_rgbuv_hist_hellinger_bwd3 prep");
     if (rc) return rc;
-    int nsplit = 1;
-    while (N * nsplit < 256 && (H * W) / (nsplit * 2) >= 8 * B3_PB) nsplit *= 2;       // one 12-wave workgroup per CU
-    constexpr int SHM = B3_SHM;
-    static_assert(SHM <= 160 * 1024, "rgbuv_hist_bwd3_kernel: LDS");
+    return launch_hist_bwd3(dtype, N, H, W, fake, gh_ws, dimg, st, "p2p_rgbuv_hist_hellinger_bwd3");
+}
+
+extern "C" int p2p_rgbuv_hist_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, const float* gh, float* dimg, void* stream) {
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0 && img && img->ptr && gh && dimg, "p2p_rgbuv_hist_bwd: bad args");
+    P2P_REQUIRE(((uintptr_t)dimg % 16) == 0, "p2p_rgbuv_hist_bwd: dimg must be 16-byte aligned");
+    return launch_hist_bwd3(dtype, N, H, W, img, gh, dimg, (hipStream_t)stream, "p2p_rgbuv_hist_bwd");
+}
+
+// ---- backward of the standalone histogram function (histogram.calculate_rgbuv_histogram under torch autograd) ----------------
+// The VJP of the normalisation and transpose (histogram.py:75-79): with T = sum raw and Hn = raw / T,
+//     gh[n][c][i][j] = (g[n][i][j][c] - sum_{c,i,j} g[n] Hn[n]) / T_n
+// One workgroup per image; both sums in a fixed order (block_sum), no float atomics.  T is summed exactly as hist_normalize_kernel
+// sums it, so Hn is the forward's value bit for bit on the default path.
+__global__ __launch_bounds__(256) void hist_normalize_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ gout, int S,
+                                                                float* __restrict__ gh) {
+    __shared__ float red[16];
+    const int n = blockIdx.x;
+    const int SS = S * S, E = 3 * SS;
+    const float* a = raw + (long long)n * E;
+    const float* g = gout + (long long)n * E;
+    float t = 0.f;
+    for (int i = threadIdx.x; i < E; i += 256) t += a[i];
+    t = block_sum(t, red);
+    float s = 0.f;
+    for (int i = threadIdx.x; i < E; i += 256) {
+        const int c = i / SS, ij = i - c * SS;
+        s += g[ij * 3 + c] * (a[i] / t);
+    }
+    s = block_sum(s, red);
+    for (int i = threadIdx.x; i < E; i += 256) {
+        const int c = i / SS, ij = i - c * SS;
+        gh[(long long)n * E + i] = (g[ij * 3 + c] - s) / t;
+    }
+}
+
+extern "C" int p2p_hist_normalize_bwd(const float* raw, const float* grad_out, int N, int size, float* gh, void* stream) {
+    P2P_REQUIRE(raw && grad_out && gh && N > 0 && size >= 2 && size <= 128, "p2p_hist_normalize_bwd: bad args (size 2..128)");
+    hist_normalize_bwd_kernel<<<dim3(N), 256, 0, (hipStream_t)stream>>>(raw, grad_out, size, gh);
+    return p2p_check_launch("p2p_hist_normalize_bwd");
+}
+
+// Backward of rgbuv_hist_general_kernel.  Per component, with ku[i] = k(u_p - d_i), kv[j] = k(v_p - d_j), A[i] = sum_j gh[i][j] kv[j]
+// and Bm[j] = sum_i gh[i][j] ku[i]:
+//     dIy += sum_i A[i] ku[i],   du = Iy sum_i A[i] k'(u_p - d_i),   dv = Iy sum_j Bm[j] k'(v_p - d_j)
+// then the chain rule of rgbuv_hist_bwd_kernel's epilogue.  One workgroup per (image, 64 pixels), lane = pixel; per component gh_c
+// (zero-padded to a multiple of 4 bins) and the pixels' kernel rows [bin][pixel] sit in LDS, wave w contracts the row blocks
+// (for A) and column blocks (for Bm) w, w+4, ... of four bins each (one broadcast 16-byte read of gh per four products), and
+// wave 0 adds the four waves' partial sums in wave order and the three components in component order: deterministic.
+#define GB_PB 64
+
+__device__ __forceinline__ float gen_kernel(float t, int method, float inv_sigma2) {
+    const float q = t * t * inv_sigma2;                   // rgbuv_hist_general_kernel's (u - d)^2 / sigma^2
+    return method == 0 ? 1.0f / (1.0f + q) : (method == 1 ? expf(-q) : q);
+}
+// k'(t) from t and k(t): -2t/sigma^2 k^2 (inverse-quadratic), -2t/sigma^2 k (RBF), 2t/sigma^2 (no kernel function)
+__device__ __forceinline__ float gen_kernel_deriv(float t, float k, int method, float inv_sigma2) {
+    const float g = 2.0f * t * inv_sigma2;
+    return method == 0 ? -g * k * k : (method == 1 ? -g * k : g);
+}
+
+static size_t general_bwd_lds(int S) {
+    const int Sp = (S + 3) & ~3;
+    return (size_t)(Sp * Sp + 2 * Sp * GB_PB + 4 * 3 * GB_PB) * sizeof(float);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rgbuv_hist_general_bwd_kernel(int H, int W, TView img, int S, int method, float inv_sigma2,
+                                                                     const float* __restrict__ gh, float* __restrict__ dimg) {
+    extern __shared__ __attribute__((aligned(16))) float gbs[];
+    const int Sp = (S + 3) & ~3;
+    float* const G = gbs;                        // gh_c [Sp][Sp], zero beyond S
+    float* const Ku = G + Sp * Sp;               // ku [Sp][64 pixels], zero beyond S
+    float* const Kv = Ku + Sp * GB_PB;           // kv [Sp][64 pixels]
+    float* const red = Kv + Sp * GB_PB;          // [4 waves][dIy, du / Iy, dv / Iy][64 pixels]
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int HW = H * W, p = blockIdx.y * GB_PB + lane;
+    const bool live = p < HW;
+    float x[3] = {1.f, 1.f, 1.f};
+    if (live) load_rgb01<T>(img, n, p, W, x);
+    float lx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lx[k] = logf(x[k] + HIST_EPS);
+    const float iy = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + HIST_EPS);
+    const float step = 6.0f / (float)(S - 1);
+    float dx[3] = {0.f, 0.f, 0.f};               // wave 0's lanes: the pixel's gradient, components added in order
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int ca, cp1, cp2;
+        comp_order(c, ca, cp1, cp2);
+        const float u = lx[ca] - lx[cp1], v = lx[ca] - lx[cp2];
+        __syncthreads();                         // the previous component's readers are done with G, Ku, Kv and red
+        const float* g = gh + ((long long)n * 3 + c) * S * S;
+        for (int idx = tid; idx < Sp * Sp; idx += 256) {
+            const int i = idx / Sp, j = idx - i * Sp;
+            G[idx] = (i < S && j < S) ? g[i * S + j] : 0.f;
+        }
+        for (int i = wave; i < Sp; i += 4) {
+            float ku = 0.f, kv = 0.f;
+            if (i < S) {
+                const float d = -3.0f + (float)i * step;
+                ku = gen_kernel(u - d, method, inv_sigma2);
+                kv = gen_kernel(v - d, method, inv_sigma2);
+            }
+            Ku[i * GB_PB + lane] = ku;
+            Kv[i * GB_PB + lane] = kv;
+        }
+        __syncthreads();
+        float s_iy = 0.f, s_u = 0.f, s_v = 0.f;
+        // A: rows i0..i0+3
+        for (int i0 = 4 * wave; i0 < Sp; i0 += 16) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < Sp; j += 4) {
+                float kv[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) kv[q] = Kv[(j + q) * GB_PB + lane];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const f32x4 g4 = *(const f32x4*)(G + (i0 + r) * Sp + j);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) a[r] = fmaf(g4[q], kv[q], a[r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = i0 + r;
+                if (i < S) {
+                    const float k = Ku[i * GB_PB + lane];
+                    s_iy = fmaf(a[r], k, s_iy);
+                    s_u = fmaf(a[r], gen_kernel_deriv(u - (-3.0f + (float)i * step), k, method, inv_sigma2), s_u);
+                }
+            }
+        }
+        // Bm: columns j0..j0+3
+        for (int j0 = 4 * wave; j0 < Sp; j0 += 16) {
+            float b[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < Sp; i += 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float ku = Ku[(i + r) * GB_PB + lane];
+                    const f32x4 g4 = *(const f32x4*)(G + (i + r) * Sp + j0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) b[q] = fmaf(g4[q], ku, b[q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = j0 + q;
+                if (j < S) s_v = fmaf(b[q], gen_kernel_deriv(v - (-3.0f + (float)j * step), Kv[j * GB_PB + lane], method, inv_sigma2), s_v);
+            }
+        }
+        red[(wave * 3 + 0) * GB_PB + lane] = s_iy;
+        red[(wave * 3 + 1) * GB_PB + lane] = s_u;
+        red[(wave * 3 + 2) * GB_PB + lane] = s_v;
+        __syncthreads();
+        if (wave == 0) {
+            float diy = 0.f, du = 0.f, dv = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                diy += red[(w * 3 + 0) * GB_PB + lane];
+                du += red[(w * 3 + 1) * GB_PB + lane];
+                dv += red[(w * 3 + 2) * GB_PB + lane];
+            }
+            du *= iy;
+            dv *= iy;
+            dx[ca] += (du + dv) / (x[ca] + HIST_EPS);
+            dx[cp1] -= du / (x[cp1] + HIST_EPS);
+            dx[cp2] -= dv / (x[cp2] + HIST_EPS);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dx[k] += diy * x[k] / iy;
+        }
+    }
+    if (wave == 0 && live) {
+        f32x4 o = {0.5f * dx[0], 0.5f * dx[1], 0.5f * dx[2], 0.f};                   // x = img*0.5+0.5; alpha has no gradient
+        *(f32x4*)(dimg + ((long long)n * HW + p) * 4) = o;
+    }
+}
+
+extern "C" int p2p_rgbuv_hist_general_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, int size, int method, float sigma,
+                                          const float* gh, float* dimg, void* stream) {
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0 && img && img->ptr && gh && dimg, "p2p_rgbuv_hist_general_bwd: bad args");
+    P2P_REQUIRE(size >= 2 && size <= 128 && sigma > 0.f && method >= 0 && method <= 2,
+                "p2p_rgbuv_hist_general_bwd: size in 2..128, sigma > 0, method 0..2");
+    P2P_REQUIRE(((uintptr_t)dimg % 16) == 0, "p2p_rgbuv_hist_general_bwd: dimg must be 16-byte aligned");
+    const long long tiles = ((long long)H * W + GB_PB - 1) / GB_PB;
+    P2P_REQUIRE(tiles <= 65535, "p2p_rgbuv_hist_general_bwd: H*W = %lld pixels exceeds %d", (long long)H * W, 65535 * GB_PB);
     static bool attr = false;
-    if (!attr)
-        attr = (int)p2p_allow_lds((const void*)rgbuv_hist_bwd3_kernel<float>, SHM, "rgbuv_hist_bwd3_kernel<float>") &
-               (int)p2p_allow_lds((const void*)rgbuv_hist_bwd3_kernel<bf16_t>, SHM, "rgbuv_hist_bwd3_kernel<bf16>");
-    P2P_DISPATCH_DTYPE(dtype, (rgbuv_hist_bwd3_kernel<T><<<dim3(N, nsplit), B3_NT, SHM, st>>>(H, W, make_view(fake), gh_ws, dimg, nsplit)));
-    return p2p_check_launch("p2p_rgbuv_hist_hellinger_bwd3");
+    if (!attr) {
+        const int most = (int)general_bwd_lds(128);
+        attr = (int)p2p_allow_lds((const void*)rgbuv_hist_general_bwd_kernel<float>, most, "rgbuv_hist_general_bwd_kernel<float>") &
+               (int)p2p_allow_lds((const void*)rgbuv_hist_general_bwd_kernel<bf16_t>, most, "rgbuv_hist_general_bwd_kernel<bf16>");
+    }
+    const float inv_sigma2 = 1.0f / (sigma * sigma);
+    P2P_DISPATCH_DTYPE(dtype, (rgbuv_hist_general_bwd_kernel<T><<<dim3(N, (unsigned)tiles), 256, general_bwd_lds(size), (hipStream_t)stream>>>(
+                                  H, W, make_view(img), size, method, inv_sigma2, gh, dimg)));
+    return p2p_check_launch("p2p_rgbuv_hist_general_bwd");
 }
 
 extern "C" int p2p_rgbuv_hist_hellinger_bwd(int dtype, int N, int H, int W, const p2p_tensor* fake, const float* hist_true,

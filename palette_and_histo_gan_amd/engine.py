@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import histogram as _histogram
 
 HALO = 2
 IN_EPS = 1e-3           # tfa InstanceNormalization default (networks.py:18,29)
@@ -1660,15 +1661,10 @@ class Pix2PixEngine:
 
     def rgbuv_histogram(self, image):
         """histogram.calculate_rgbuv_histogram (histogram.py:35-81) of a dense f32 (B,S,S,4) batch in [-1,1]:
-        returns the normalised (B,64,64,3) f32 device tensor in the reference's layout."""
+        returns the normalised (B,64,64,3) f32 device tensor in the reference's layout, differentiable with respect to `image`
+        (histogram.RGBuvHistogram: the loss hooks of train_step_rgba_hooked reach the generator through it)."""
         B = int(image.shape[0])
-        S = self.S
-        img_t = self._to_device(image, 4, B)
-        raw = torch.empty(B * 3 * 64 * 64, dtype=torch.float32, device=self.device)
-        L.call("p2p_rgbuv_hist_fwd", L.F32, B, S, S, C.byref(L.Tensor(img_t.data_ptr(), S * S, S, 4)), _p(raw), _stream())
-        out = torch.empty((B, 64, 64, 3), dtype=torch.float32, device=self.device)
-        L.call("p2p_hist_normalize", _p(raw), B, _p(out), _stream())
-        return out
+        return _histogram.rgbuv_histogram(self._to_device(image, 4, B))
 
     # ------------------------------------------------------------------ train step (indexed model)
     def train_step_indexed(self, source_idx, real_idx, lambda_segmentation, masks=None, global_batch=None,
