@@ -358,6 +358,14 @@ int p2p_rgbuv_hist_general_bwd(int dtype, int N, int H, int W, const p2p_tensor*
 int p2p_softmax_cce_argmax(int dtype, int N, int H, int W, int C, const p2p_tensor* z, const p2p_tensor* target,
                            const p2p_tensor* fake_idx, float grad_scale, float inv_count, const p2p_tensor* dz,
                            float* probs_out, float* loss_part, float* loss_out, void* stream);
+/* VJP of softmax over the last dimension, plus an optional direct logits gradient (the loss hooks of the indexed train step):
+ *   dz[n,y,x,c] = scale * ( gz[m,c] + p[m,c] * (gp[m,c] - sum_k p[m,k] * gp[m,k]) ),   m = (n*H + y)*W + x
+ * probs, gp, gz: dense f32 [N*H*W][C], 16-byte aligned; gp or gz may be NULL (absent = 0; probs is only read with gp).  dz: view
+ * in `dtype` (16-byte aligned pixels, written only at the view's own pixels and channels, halo untouched).  C == 256 (anything
+ * else: negative return code + p2p_last_error).  f32 arithmetic, except sum_k p*gp and gp - sum_k p*gp in f64 (they cancel where
+ * one class dominates).  Deterministic: every pixel is reduced by a fixed set of lanes in a fixed order, no atomics. */
+int p2p_softmax_bwd(int dtype, int N, int H, int W, int C, const float* probs, const float* gp, const float* gz,
+                    float scale, const p2p_tensor* dz, void* stream);
 /* tf.argmax(probs, axis=-1, output_type=int32) on dense f32 probabilities [M][C]; ties -> lowest index. */
 int p2p_argmax_lastdim(const float* probs, long long M, int C, int* out, void* stream);
 

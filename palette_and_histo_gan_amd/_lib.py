@@ -82,6 +82,7 @@ SIGNATURES = {
     "p2p_rgbuv_hist_bwd": [_i, _i, _i, _i, _TP, _vp, _vp, _vp],
     "p2p_rgbuv_hist_general_bwd": [_i, _i, _i, _i, _TP, _i, _i, _f, _vp, _vp, _vp],
     "p2p_softmax_cce_argmax": [_i, _i, _i, _i, _i, _TP, _TP, _TP, _f, _f, _TP, _vp, _vp, _vp, _vp],
+    "p2p_softmax_bwd": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _TP, _vp],
     "p2p_argmax_lastdim": [_vp, _ll, _i, _vp, _vp],
     "p2p_head_dgrad": [_i, _i, _i, _i, _i, _i, _TP, _vp, _i, _TP, _vp],
     "p2p_head_softmax_cce": [_i, _i, _i, _i, _i, _i, _TP, _vp, _vp, _TP, _TP, _f, _f, _TP, _vp, _vp, _vp, _vp],

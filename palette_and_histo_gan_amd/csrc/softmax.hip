@@ -210,6 +210,62 @@ __global__ __launch_bounds__(256) void softmax256_kernel(int N, PixDec dec, TVie
     }
 }
 
+// VJP of the 256-way softmax for the loss hooks of the indexed train step: dz = scale * (gz + p * (gp - <p, gp>)).  The layout of
+// softmax256_kernel: 16 lanes own one pixel (16 consecutive classes each, 16-byte accesses), the per-pixel dot product is a 4-level
+// butterfly inside the 16-lane group (fixed order: bit-reproducible), f32 arithmetic except for the dot product and
+// the difference gp - <p, gp> (f64, below).  A pure stream: per pixel up to 3 KB of f32 in, 0.5 / 1 KB
+// out; every operand of a pixel is loaded before the first use, 8 (gp only) or 12 16-byte loads in flight per lane.
+template <typename T, bool GP, bool GZ>
+__global__ __launch_bounds__(256) void softmax256_bwd_kernel(unsigned M, PixDec dec, const float* __restrict__ probs,
+                                                             const float* __restrict__ gp, const float* __restrict__ gz, float scale,
+                                                             TView dz) {
+    constexpr int VN = 16 / sizeof(T);
+    typedef __attribute__((__vector_size__(16))) T vec_t;
+    const int sub = threadIdx.x & 15;
+    const unsigned gid = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, ngroups = (gridDim.x * blockDim.x) >> 4;
+    for (unsigned m = gid; m < M; m += ngroups) {
+        const long long e = (long long)m * 256 + sub * 16;
+        f32x4 p[4], g[4], h[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (GP) { p[q] = *(const f32x4*)(probs + e + 4 * q); g[q] = *(const f32x4*)(gp + e + 4 * q); }
+            if (GZ) h[q] = *(const f32x4*)(gz + e + 4 * q);
+        }
+        // <p, gp> and gp - <p, gp> in f64: where one class dominates, gp_top - <p, gp> cancels to ~(1 - p_top) gp_top and an f32
+        // dot product would leave ~1e-4 of the pixel's largest gradient as rounding (measured); a few f64 operations per element
+        // are free in a stream at HBM rate
+        double dot = 0.0;
+        if (GP) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dot = fma((double)p[q][k], (double)g[q][k], dot);
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+        }
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float d = 0.f;
+                if (GP) d = p[q][k] * (float)((double)g[q][k] - dot);
+                if (GZ) d = h[q][k] + d;
+                v[4 * q + k] = (GP || GZ) ? d * scale : 0.f;
+            }
+        int n, y, x;
+        dec(m, n, y, x);
+        T* dp = (T*)dz.ptr + dz.off(n, y, x) + sub * 16;
+#pragma unroll
+        for (int q = 0; q < 16 / VN; ++q) {
+            vec_t r;
+#pragma unroll
+            for (int k = 0; k < VN; ++k) r[k] = from_f32<T>(v[q * VN + k]);
+            *(vec_t*)(dp + q * VN) = r;
+        }
+    }
+}
+
 // argmax over the last dimension of given probabilities (pix2pix_model.py:286): int32, ties -> lowest index
 __global__ void argmax_lastdim_kernel(const float* __restrict__ p, long long M, int C, int* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -271,4 +327,29 @@ extern "C" int p2p_argmax_lastdim(const float* probs, long long M, int C, int* o
     if (blocks > 2048) blocks = 2048;
     argmax_lastdim_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(probs, M, C, out);
     return p2p_check_launch("p2p_argmax_lastdim");
+}
+
+extern "C" int p2p_softmax_bwd(int dtype, int N, int H, int W, int C, const float* probs, const float* gp, const float* gz,
+                               float scale, const p2p_tensor* dz, void* stream) {
+    P2P_REQUIRE(C == 256, "p2p_softmax_bwd: C = %d, only the 256-way palette softmax is supported", C);
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31), "p2p_softmax_bwd: bad shape %d x %d x %d", N, H, W);
+    P2P_REQUIRE(dz && dz->ptr && (!gp || probs), "p2p_softmax_bwd: null pointer");
+    const int vn = dtype == P2P_BF16 ? 8 : 4;
+    P2P_REQUIRE(((uintptr_t)dz->ptr % 16) == 0 && dz->ld % vn == 0 && dz->ld >= C && ((uintptr_t)probs % 16) == 0 &&
+                    ((uintptr_t)gp % 16) == 0 && ((uintptr_t)gz % 16) == 0,
+                "p2p_softmax_bwd: operands must be 16-byte aligned (dz: whole 16-byte chunks per pixel)");
+    const unsigned M = (unsigned)N * H * W;
+    long long blocks = ((long long)M + 15) / 16;      // 16 pixel groups per 256-thread workgroup
+    if (blocks > 4096) blocks = 4096;
+    hipStream_t st = (hipStream_t)stream;
+    const PixDec dec = PixDec::make(H, W);
+    const TView d = make_view(dz);
+#define P2P_SMBWD(GP_, GZ_) \
+    P2P_DISPATCH_DTYPE(dtype, (softmax256_bwd_kernel<T, GP_, GZ_><<<dim3((unsigned)blocks), 256, 0, st>>>(M, dec, probs, gp, gz, scale, d)))
+    if (gp && gz) P2P_SMBWD(true, true);
+    else if (gp) P2P_SMBWD(true, false);
+    else if (gz) P2P_SMBWD(false, true);
+    else P2P_SMBWD(false, false);
+#undef P2P_SMBWD
+    return p2p_check_launch("p2p_softmax_bwd");
 }

@@ -1698,7 +1698,7 @@ class Pix2PixEngine:
             self._end_record(key, True)
         return out
 
-    def _train_step_indexed_body(self, P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update):
+    def _pack_indexed(self, P, B, src_t, real_t):
         S = self.S
         self._bind_batch(src_t, real_t)
         if self.full_pixels and self.in_ch == 1 and self.src_ch == 8 and self.dcat_ch == 8:
@@ -1709,6 +1709,10 @@ class Pix2PixEngine:
         else:
             self._pack_source(P, src_t, with_disc=True)
             self._pack(P, real_t, P["dcat"].view(coff=0), 1, ptr=self._slot_real)
+
+    def _train_step_indexed_body(self, P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update):
+        S = self.S
+        self._pack_indexed(P, B, src_t, real_t)
         self._early_side(P, masks, apply_update)
         fused = (self.use_mfma and self.use_head_fused and
                  L.lib().p2p_head_softmax_ok(self.dtype, B, S, S, self.c6_ch, self.out_ch))
@@ -1746,6 +1750,67 @@ class Pix2PixEngine:
         L.call("p2p_finish_losses", _p(self.losses), 5, 6, 0.0, float(lambda_segmentation), self._slot_out, _stream())
         self.step_count += 1
         return out[:7]
+
+    def train_step_indexed_hooked(self, source_idx, real_idx, generator_loss, discriminator_loss, masks=None, apply_update=True):
+        """Pix2PixIndexedModel.train_step (pix2pix_model.py:295-325) for a subclass that overrides the loss hooks (the palette-index
+        counterpart of train_step_rgba_hooked).  generator_loss(fake_predicted, fake_image, real_image) is handed the discriminator's
+        output for [argmax, source], the f32 softmax probabilities (B,S,S,256) and the one-hot target; discriminator_loss(real_predicted,
+        fake_predicted) as in the RGBA step.  The probabilities carry their logits as `_keras_logits` (Keras caches them on a softmax
+        output; pix2pix_model.CategoricalCrossentropy evaluates on them), so autograd returns d(loss)/d(probs) AND d(loss)/d(logits);
+        p2p_softmax_bwd maps both to the head's pre-activation gradient.  The argmax blocks every gradient from D to G (:292,306):
+        the gradient of generator_loss with respect to fake_predicted is computed and discarded.
+        Unfused head, four f32 (B,S,S,256) tensors (probabilities, logits, one-hot, and the hooks' gradients): opt-in only.
+        Returns [g_total, g_adv, g_l1, g_4th or 0, d_total, d_real, d_fake].  Single GPU, not replayed (the hooks are host code)."""
+        assert self.head == "softmax" and self.in_ch == 1, "the RGBA models have train_step_rgba_hooked"
+        B = int(source_idx.shape[0])
+        P = self.plan(B)
+        S, h2, Cn = self.S, self.S // 2, self.out_ch
+        self._dp, self._batch_offset = None, 0
+        src_t = self._to_device(source_idx, 1, B, is_int=True)
+        real_t = self._to_device(real_idx, 1, B, is_int=True)
+        self._pack_indexed(P, B, src_t, real_t)
+        self._early_side(P, masks, apply_update)
+        self.generator_forward(P, masks, head=True)
+        real_view, fake_view = P["dcat"].view(coff=0), P["dcat"].view(coff=0, n0=B)
+        bufs = P.get("hook_idx")
+        if bufs is None:        # ~0.5 GB each at B = 128: kept with the plan, not allocated per step
+            bufs = P["hook_idx"] = tuple(torch.empty((B, S, S, Cn), dtype=torch.float32, device=self.device) for _ in range(3))
+        probs32, z32, onehot = bufs
+        # softmax + argmax (written into the discriminator's fake half) + the f32 probabilities; no loss, no gradient
+        L.call("p2p_softmax_cce_argmax", self.dtype, B, S, S, Cn, C.byref(P["z"].view()), C.byref(real_view), C.byref(fake_view),
+               0.0, 0.0, None, _p(probs32), _p(self._softmax_part()), _p(self.losses, 14), _stream())
+        L.call("p2p_unpack", self.dtype, B, S, S, Cn, C.byref(P["z"].view()), _p(z32), _stream())
+        onehot.zero_()
+        onehot.view(-1, Cn).scatter_(1, real_t.view(-1, 1).long(), 1.0)
+        self.discriminator_forward(P, 2 * B)
+        logits = P["logits"].t.detach().float().view(2 * B, h2, h2, 1)
+        lg_d = logits.clone().requires_grad_(True)
+        d_loss = discriminator_loss(lg_d[:B], lg_d[B:])
+        d_loss[0].backward()
+        lg_g = logits[B:].clone().requires_grad_(True)
+        probs = probs32.detach().requires_grad_(True)
+        probs._keras_logits = z32.detach().requires_grad_(True)
+        g_loss = generator_loss(lg_g, probs, onehot)
+        g_loss[0].backward()
+        grad = lambda t: None if t.grad is None else t.grad.contiguous()        # noqa: E731  (absent: zero)
+        gp, gz = grad(probs), grad(probs._keras_logits)
+        inner = slice(HALO, HALO + h2)
+        P["dld"].t[:, inner, inner, 0] = (torch.zeros_like(lg_d) if lg_d.grad is None else lg_d.grad).view(2 * B, h2, h2).to(self.tdt)
+        P["hook_keep"] = (gp, gz, lg_d, lg_g, probs)
+        L.call("p2p_softmax_bwd", self.dtype, B, S, S, Cn, _p(probs32), NULL if gp is None else _p(gp), NULL if gz is None else _p(gz),
+               1.0, C.byref(P["dz"].view()), _stream())
+        P["skip_g_through_d"] = True
+        P["head_dbias_done"] = False        # the plan is shared with the fused step, whose head sums the bias gradient itself
+        self.discriminator_backward(P, B)
+        self.generator_backward(P)
+        head = self._adam_head(apply_update)
+        self.side.join()
+        if apply_update:
+            self.apply_adam(g_from=head)
+        self.step_count += 1
+        vals = [g_loss[0], g_loss[1], g_loss[2], g_loss[3] if len(g_loss) > 3 else torch.zeros((), device=self.device),
+                d_loss[0], d_loss[1], d_loss[2]]
+        return torch.stack([v.detach().reshape(()).float() for v in vals])
 
     def _softmax_part(self):
         """workspace of p2p_softmax_cce_argmax: one (CCE, L1) partial per workgroup (include/p2pgan.h)"""

@@ -13,8 +13,10 @@ additionally RETURNS (g_loss_tuple, d_loss_tuple) as device scalars, and tolerat
 
 The step is FUSED: generator_loss / discriminator_loss of the classes below are evaluated by the HIP kernels inside
 engine.train_step_* together with their gradients (there is no autograd tape here).  The methods exist with the
-reference's signatures for standalone evaluation, but a SUBCLASS that overrides one of them cannot change the fused step;
-train_step detects that and raises instead of silently ignoring the override.
+reference's signatures for standalone evaluation.  A SUBCLASS that overrides one of them cannot change the fused step:
+train_step detects the override and runs the hooked step instead (hooks under torch autograd, gradients into the backward
+kernels); the palette-index model takes that path only when the subclass sets `differentiable_loss_hooks = True`, and raises
+otherwise instead of silently ignoring the override.
 Extra keyword arguments (dtype, img_size, device, data_parallel, seed) are build-added; defaults reproduce the reference.
 
 Data parallelism (build-added): with `data_parallel`, every rank agrees on the same GLOBAL batch (same
@@ -53,12 +55,16 @@ class BinaryCrossentropy:
 class CategoricalCrossentropy:
     """tf.keras.losses.CategoricalCrossentropy(from_logits=False) (pix2pix_model.py:265) for standalone evaluation.
     Keras 2.9 evaluates it on the logits cached by the softmax activation (softmax_cross_entropy_with_logits) -- that is what
-    train_step's fused kernel computes (log-sum-exp form, csrc/softmax.hip) and what `logits=` selects here.  Handed
-    probabilities alone, Keras' documented fallback applies: p /= sum p; p = clip(p, 1e-7, 1 - 1e-7); mean of -sum t log p.
+    train_step's fused kernel computes (log-sum-exp form, csrc/softmax.hip) and what `logits=` selects here.  As in Keras, a
+    y_pred that carries the cached logits as `y_pred._keras_logits` (the probabilities the indexed model's hooked train step hands
+    its generator_loss) is evaluated on them; a tensor derived from it loses the attribute.  Handed probabilities alone, Keras'
+    documented fallback applies: p /= sum p; p = clip(p, 1e-7, 1 - 1e-7); mean of -sum t log p.
     The two agree to < 1e-6 unless a target probability is below 1e-7, where the fallback is capped at -log 1e-7 = 16.1 per
     pixel and the logits form is not."""
 
     def __call__(self, y_true, y_pred, logits=None):
+        if logits is None:
+            logits = getattr(y_pred, "_keras_logits", None)
         if logits is not None:
             z = torch.as_tensor(logits, dtype=torch.float32)
             t = torch.as_tensor(y_true, dtype=torch.float32).to(z.device)
@@ -166,7 +172,9 @@ class Pix2PixModel(S2SModel):
         Pix2PixIndexedModel) run fused: losses and gradients in one kernel sequence, no tape.  A subclass that OVERRIDES
         generator_loss / discriminator_loss (the hooks are part of the boundary) gets `engine.train_step_rgba_hooked`:
         the kernels run forward, the hooks are evaluated on torch tensors with autograd, their gradients enter the backward kernels.
-        The palette-index model's step is fused around its softmax head and argmax: overriding ITS hooks is refused."""
+        The palette-index model's step is fused around its softmax head and argmax: overriding ITS hooks is refused unless the
+        subclass opts in with `differentiable_loss_hooks = True` (engine.train_step_indexed_hooked: unfused head, four f32
+        (B,S,S,256) tensors, slower)."""
         if self._hooks_checked:
             return
         known = (Pix2PixModel, Pix2PixHistogramModel, Pix2PixIndexedModel)
@@ -175,11 +183,12 @@ class Pix2PixModel(S2SModel):
             owner = next((c for c in type(self).__mro__ if hook in c.__dict__), None)
             if owner not in known:
                 custom.append(hook)
-        if custom and isinstance(self, Pix2PixIndexedModel):
+        if custom and isinstance(self, Pix2PixIndexedModel) and not self.differentiable_loss_hooks:
             raise NotImplementedError(
                 f"{type(self).__name__}.{custom[0]} overrides the reference's loss, but the palette-index train_step is one fused "
                 f"sequence of HIP kernels around the softmax head and its argmax (no gradient path from the discriminator, "
-                f"pix2pix_model.py:295-325): add the loss to engine.train_step_indexed or subclass train_step.")
+                f"pix2pix_model.py:295-325): set `differentiable_loss_hooks = True` on the subclass to train through the "
+                f"unfused hooked step (engine.train_step_indexed_hooked), or subclass train_step.")
         if custom and self.data_parallel is not None:
             raise NotImplementedError("overridden loss hooks run on one GPU (the hooked step issues no collectives)")
         self._custom_hooks = bool(custom)
@@ -301,7 +310,11 @@ class Pix2PixHistogramModel(Pix2PixAugmentedModel):
 
 
 class Pix2PixIndexedModel(Pix2PixModel):
-    """pix2pix_model.py:261-330"""
+    """pix2pix_model.py:261-330.  A subclass that overrides generator_loss / discriminator_loss must also set
+    `differentiable_loss_hooks = True`: its hooks then run under autograd beside the kernels (engine.train_step_indexed_hooked),
+    at the price of the unfused head and four f32 (B,S,S,256) tensors per step."""
+
+    differentiable_loss_hooks = False
 
     def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_segmentation=0.5, **kw):
         super().__init__(train_ds, test_ds, model_name, architecture_name, 0., **kw)      # lambda_l1 = 0 (:263)
@@ -350,7 +363,9 @@ class Pix2PixIndexedModel(Pix2PixModel):
         self._check_hooks()
         source_image, real_image, _ = batch
         (src, real), Bg, lo, dp = self._shard(batch, [source_image, real_image])
-        if len(src) == 0:
+        if self._custom_hooks:
+            out = self.engine.train_step_indexed_hooked(src, real, self.generator_loss, self.discriminator_loss)
+        elif len(src) == 0:
             out = self.engine.train_step_empty(0.0, lambda_aux=self.lambda_segmentation, dp=dp)
         else:
             out = self.engine.train_step_indexed(src, real, self.lambda_segmentation, global_batch=Bg, dp=dp, batch_offset=lo)
