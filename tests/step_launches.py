@@ -8,6 +8,8 @@ Convolutions are written in the tap form of include/p2pgan.h:
   op W: dW[kh,kw,g,d] = sum_{n,y,x} hi[n, s*y+kh-1, s*x+kw-1, g] lo[n,y,x,d]
 with a zero border of 1 pixel before and 2 after (TF SAME for k=4: (1,1) at stride 2, (1,2) at stride 1).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -135,3 +137,38 @@ def per_tap_err(got, ref):
     """weight gradient [4,4,Cg,Cd]: max over taps of max|got - ref| / max|ref| within the tap"""
     got, ref = np.asarray(got, np.float64).reshape(16, -1), np.asarray(ref, np.float64).reshape(16, -1)
     return float((np.abs(got - ref).max(axis=1) / (np.abs(ref).max(axis=1) + 1e-30)).max())
+
+
+# ---------------------------------------------------------------------------------------------------------------- step plumbing
+def keras_adam(p, g, m, v, t, lr, b1, b2, eps):
+    """one Keras (OptimizerV2) Adam step in float64, t = iteration count after the increment (pix2pix_model.py:28-29): returns
+    (p, m, v).  eps is added to sqrt(v) outside the bias correction, which lives in the step size lr_t.  The arrays are float64
+    numpy arrays or torch tensors (the GPU test evaluates the whole flat buffers on the device)."""
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+    return p - lr_t * m / (v ** 0.5 + eps), m, v
+
+
+def bf16_round(x):
+    """float32 values rounded to the nearest bfloat16, ties to even (what the kernels' from_f32 and torch's cast do), as float32"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    return (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+
+
+_M64 = (1 << 64) - 1
+
+
+def dropout_mask(n, seed, counter, group0=0):
+    """the keep mask of p2p_dropout_mask(_dev) (optim.hip dropout_mask_kernel): element 8*i+k is bit 8*k+3 of
+    z = splitmix64(seed * 0x9E3779B97F4A7C15 + counter * 0xD1B54A32D192ED03 + (i + group0)), with the generator's increment
+    0x9E3779B97F4A7C15 added before the finaliser; counter = counter_dev * 16 + salt for the device form.  uint8 [n]."""
+    base = (int(seed) * 0x9E3779B97F4A7C15 + int(counter) * 0xD1B54A32D192ED03 + int(group0) + 0x9E3779B97F4A7C15) & _M64
+    with np.errstate(over="ignore"):
+        z = np.uint64(base) + np.arange((n + 7) // 8, dtype=np.uint64)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    bits = (z[:, None] >> (np.arange(8, dtype=np.uint64) * np.uint64(8) + np.uint64(3))) & np.uint64(1)
+    return bits.reshape(-1)[:n].astype(np.uint8)

@@ -58,3 +58,45 @@ def test_moment_err_is_per_image_and_channel():
     m2 = m.copy()
     m2[1, 0] += 0.01 * np.sqrt(v[1, 0])          # small next to the other channel's scale, 1 % of this channel's deviation
     assert abs(SL.moment_err(m2, v, x) - 0.01) < 1e-9
+
+
+def test_keras_adam_equals_the_oracle_restatement():
+    from oracle import np_restatement as npr
+    rng = np.random.default_rng(7)
+    n = 257
+    p = rng.normal(size=n) * 0.02
+    g = rng.normal(size=n) * 10.0 ** rng.integers(-8, 1, size=n)
+    g[::17] = 0.0
+    m, v = rng.normal(size=n) * 1e-3, rng.random(size=n) * 1e-4
+    for t in (1, 3, 50):
+        want = npr.keras_adam_step(p, g, m, v, t, lr=2e-4, b1=0.5, b2=0.999, eps=1e-7)
+        got = SL.keras_adam(p, g, m, v, t, 2e-4, 0.5, 0.999, 1e-7)
+        for a, b in zip(got, want):
+            np.testing.assert_allclose(a, b, rtol=1e-15, atol=0)
+
+
+def test_dropout_mask_restatement_is_splitmix64():
+    # the first output of SplitMix64 seeded with 0 is 0xE220A8397B1DCDAF: bit 3 of its bytes, lowest first
+    assert SL.dropout_mask(8, 0, 0, 0).tolist() == [1, 1, 1, 1, 1, 1, 0, 0]
+    z = 0xE220A8397B1DCDAF
+    assert [(z >> (8 * k + 3)) & 1 for k in range(8)] == [1, 1, 1, 1, 1, 1, 0, 0]
+    # the call counter, the seed and the element group enter the generator's state linearly: group g of (seed, counter) is the
+    # first group of the state shifted by g, and a tail shorter than 8 is a prefix
+    full = SL.dropout_mask(8 * 5, 1234, 16 * 7 + 3, 40)
+    assert np.array_equal(SL.dropout_mask(8, 1234, 16 * 7 + 3, 43), full[24:32])
+    assert np.array_equal(SL.dropout_mask(37, 1234, 16 * 7 + 3, 40), full[:37])
+    m = SL.dropout_mask(1 << 16, 5, 9)
+    assert set(np.unique(m).tolist()) == {0, 1} and abs(m.mean() - 0.5) < 0.01
+
+
+def test_bf16_round_matches_torch_at_ties():
+    # values exactly halfway between two bfloat16 numbers, with even and odd lower neighbours, and their neighbours
+    hi = np.arange(0x3F80, 0x3F90, dtype=np.uint32) << 16
+    ties = (hi | 0x8000).view(np.float32)
+    near = np.concatenate([ties, (hi | 0x7FFF).view(np.float32), (hi | 0x8001).view(np.float32), -ties,
+                           np.float32([0.0, -0.0, 1e-40, 3.0e38, 1.0, -2.5])])
+    want = torch.as_tensor(near).to(torch.bfloat16).float().numpy()
+    assert np.array_equal(SL.bf16_round(near).view(np.uint32), want.view(np.uint32))
+    rng = np.random.default_rng(8)
+    x = (rng.normal(size=4096) * 10.0 ** rng.integers(-6, 6, size=4096)).astype(np.float32)
+    assert np.array_equal(SL.bf16_round(x).view(np.uint32), torch.as_tensor(x).to(torch.bfloat16).float().numpy().view(np.uint32))

@@ -10,6 +10,13 @@ an entry point with a checker below is re-issued with the recorded integer / flo
   the tail of the buffer) holds a sentinel that must be bit-for-bit unchanged;
 - fused InstanceNorm statistics (slot partials) equal the f64 moments of the stored output;
 - a second launch on the same inputs is bit-identical.
+The losses, reductions, packing, weight copies, Adam and the dropout RNG are checked the same way: losses and column sums against
+f64 (loss rows as sums of their P2P_LOSS_BLOCKS partials), packing and weight copies bit for bit against the dtype rounding of
+their input with zero padding, Adam against the f64 Keras step at t = 1 and t = 3 on flat buffers laid out like the recorded
+store (every element no task covers keeps its sentinel), the masks bit for bit against tests/step_launches.dropout_mask.  Device
+task tables are copied from the engine while it is alive and re-issued as fresh tables over test-owned buffers.  Forms that no
+benchmarked step issues are re-issued with hand-written arguments (test_entry_points_no_benchmarked_step_issues), and
+test_one_keras_update_per_parameter_per_step checks that a replayed step moves every parameter by exactly one Adam step.
 """
 import ctypes as C
 import gc
@@ -38,19 +45,8 @@ CONFIGS = [("c1", "bf16"), ("c2", "bf16"), ("c3", "bf16"), ("c4", "bf16"), ("c5"
 # entry points of a recorded step that this file does not re-issue, with the reason.  A call that is neither here nor in
 # CHECKERS fails the test: a new entry point cannot slip past.
 OUT_OF_SCOPE = {
-    "p2p_adam_flat": "optimizer", "p2p_adam_flat_dev": "optimizer", "p2p_adam_tick": "optimizer",
-    "p2p_adam_prep_batched": "optimizer", "p2p_weight_prep": "packing (weight copies)",
-    "p2p_weight_prep_pad": "packing (weight copies)", "p2p_weight_prep_batched": "packing (weight copies)",
-    "p2p_pack_input": "packing", "p2p_pack_input_multi": "packing", "p2p_pack_pair": "packing", "p2p_pack_pair_idx": "packing",
-    "p2p_unpack": "packing",
-    "p2p_bce_logits": "loss", "p2p_bce_logits_pad8": "loss", "p2p_loss_partials_sum": "loss", "p2p_tanh_l1_fwd": "loss",
-    "p2p_tanh_l1_fwd_pair": "loss", "p2p_tanh_l1_bwd": "loss", "p2p_tanh_l1_bwd_pad8": "loss", "p2p_finish_losses": "loss",
-    "p2p_hellinger_fwd": "loss", "p2p_hellinger_finish": "loss", "p2p_hist_normalize": "loss",
-    "p2p_colsum": "loss / parameter-gradient reduction", "p2p_colsum_batched": "parameter-gradient reduction",
-    "p2p_view_colsum": "bias-gradient reduction",
-    "p2p_dropout_mask": "dropout RNG", "p2p_dropout_mask_dev": "dropout RNG", "p2p_counter_add": "dropout RNG",
     "p2p_event_record": "stream operation", "p2p_stream_wait_event": "stream operation", "p2p_arm_stop_event": "stream operation",
-    "p2p_event_create": "stream operation",
+    "p2p_event_create": "stream operation", "p2p_disarm_stop_event": "stream operation",
 }
 
 
@@ -134,11 +130,17 @@ def _decode(name, args, blocks):
         dtype = vals[2]
     elif name in ("p2p_wgemm", "p2p_wgemm_edge", "p2p_wgrad_small", "p2p_norm_act_fwd", "p2p_norm_act_fwd_tail",
                   "p2p_norm_act_bwd", "p2p_act_bwd", "p2p_rgbuv_points", "p2p_rgbuv_hist_fwd3", "p2p_rgbuv_hist_hellinger_bwd3",
-                  "p2p_head_dgrad", "p2p_head_softmax_cce"):
+                  "p2p_head_dgrad", "p2p_head_softmax_cce", "p2p_bce_logits", "p2p_bce_logits_pad8", "p2p_tanh_l1_fwd",
+                  "p2p_tanh_l1_fwd_pair", "p2p_tanh_l1_bwd", "p2p_tanh_l1_bwd_pad8", "p2p_view_colsum", "p2p_pack_input",
+                  "p2p_pack_input_multi", "p2p_pack_pair", "p2p_pack_pair_idx", "p2p_unpack", "p2p_weight_prep", "p2p_weight_prep_pad",
+                  "p2p_weight_prep_batched", "p2p_adam_prep_batched"):
         dtype = vals[0]
     out = []
     for t, v in zip(types, vals):
-        if t is L._TP:
+        if t is L._TP and name == "p2p_pack_input_multi":          # an array of ndst views
+            out.append(("views", tuple(tuple(sorted((k, x) for k, x in _view_desc(d, _esz(dtype), blocks).items() if k != "ptr"))
+                                       for d in list(v)[:vals[8]])))
+        elif t is L._TP:
             out.append(None if v is None else ("view", _view_desc(v, _esz(dtype), blocks)))
         elif t is L._GP:
             out.append(None if v is None else ("gsrc", _gsrc_desc(v, dtype, blocks)))
@@ -152,19 +154,87 @@ def _decode(name, args, blocks):
     return out
 
 
+def _raw_ptr(v):
+    v = _val(v)
+    return v.value if isinstance(v, C.c_void_p) else v
+
+
+def _in_store(eng, ptr, what):
+    """(network, store, element offset) of a pointer into one of the flat params / grads / m / v buffers"""
+    for sid, store in (("G", eng.G), ("D", eng.D)):
+        for buf in (store.params, store.grads, store.m, store.v):
+            a = buf.data_ptr()
+            if a <= ptr < a + 4 * buf.numel():
+                assert (ptr - a) % 4 == 0, what
+                return sid, store, (ptr - a) // 4
+    raise AssertionError(f"{what}: pointer {ptr:#x} is in no flat parameter buffer")
+
+
+def _tables(eng):
+    """host copies of the engine's device-resident argument tables, by device address: the p2p_prep_task tables of the weight
+    copies (_prep_table) and of the fused Adam (_adam_tables), and the part_tasks rows of every plan's dgamma / dbeta reduction"""
+    out = {}
+    for raw, *_ in list(eng._prep_table.values()) + list(eng._adam_tables.values()):
+        if raw is not None:
+            out[raw.data_ptr()] = ("prep", raw.cpu().numpy().tobytes())
+    for P in eng.plans.values():
+        if P.get("part_tasks") is not None:
+            out[P["part_tasks"].data_ptr()] = ("colsum", tuple(tuple(r) for r in P["part_tasks"].cpu().tolist()))
+    return out
+
+
+def _decode_tasks(eng, raw, ntasks, what):
+    """p2p_prep_task entries -> (Cg, Cd, wn_rows, wn_cols, wt_rows, wt_cols, has_wn, has_wt, tiles_g, tiles_d, first_block,
+    network of the master, element offset of the master in its params buffer)"""
+    arr = (L.PrepTask * ntasks).from_buffer_copy(raw[:C.sizeof(L.PrepTask) * ntasks])
+    out = []
+    for t in arr:
+        sid, store, off = _in_store(eng, t.w, what)
+        assert t.w == store.params.data_ptr() + 4 * off, f"{what}: a task's master is not in params"
+        out.append((t.Cg, t.Cd, t.wn_rows, t.wn_cols, t.wt_rows, t.wt_cols, int(bool(t.wn)), int(bool(t.wt)), t.tiles_g, t.tiles_d,
+                    t.first_block, sid, off))
+    return tuple(out)
+
+
+def _decode_device_args(eng, tables, name, args, dec):
+    """the arguments _decode cannot read from the pointer alone: device task tables (copied while the engine is alive; a pointer
+    that is none of the engine's tables fails) and positions inside the flat parameter stores"""
+    if name in ("p2p_weight_prep_batched", "p2p_adam_prep_batched", "p2p_colsum_batched"):
+        i = {"p2p_weight_prep_batched": 1, "p2p_adam_prep_batched": 2, "p2p_colsum_batched": 1}[name]
+        ptr = _raw_ptr(args[i])
+        kind, data = tables.get(ptr, (None, None))
+        assert kind == ("colsum" if name == "p2p_colsum_batched" else "prep"), \
+            f"{name}: argument table {ptr:#x} is none of the engine's tables"
+        dec[i] = ("tasks", data if kind == "colsum" else _decode_tasks(eng, data, int(_val(args[i + 1])), name))
+    if name == "p2p_adam_prep_batched":
+        sid, store, off = _in_store(eng, _raw_ptr(args[5]), name)
+        assert off == 0, f"{name}: params is not the start of a store"
+        dec[5] = ("store", sid, store.numel)
+    if name == "p2p_colsum_batched":
+        sid, store, off = _in_store(eng, _raw_ptr(args[4]), name)
+        dec[4] = ("store", sid, store.grads.numel(), off)
+    if name == "p2p_adam_flat_dev":
+        sid, store, off = _in_store(eng, _raw_ptr(args[0]), name)
+        dec[0] = ("store", sid, store.numel, off)
+    return dec
+
+
 def _signature(name, dec):
     key = []
     for d in dec:
-        if isinstance(d, tuple) and d[0] != "ptr":
+        if isinstance(d, tuple) and d[0] in ("view", "gsrc"):
             key.append((d[0],) + tuple(sorted((k, v) for k, v in d[1].items() if k != "ptr")))
         else:
             key.append(d)
     return (name,) + tuple(key[:-1])           # the last argument is the stream
 
 
-def harvest(cfg, dtype_name):
-    """unique launch signatures of the recorded step of one bench config: {signature: (name, decoded args)}, and the raw count"""
+def harvest(cfg, dtype_name, fuse_adam=None):
+    """unique launch signatures of the recorded step of one bench config: {signature: (name, decoded args)}, and the raw count.
+    fuse_adam: the engine's switch if not None (bench.py runs the default)"""
     eng, step = _build(cfg, dtype_name)
+    if fuse_adam is not None:
+        eng.fuse_adam = fuse_adam
     try:
         for _ in range(2):         # the first step of a kind is eager, the second one is recorded (_begin_record)
             step()
@@ -173,13 +243,14 @@ def harvest(cfg, dtype_name):
         rec = next(iter(eng._replays.values()))[1]
         assert rec, f"{cfg}: empty recording"
         blocks = _blocks()
+        tables = _tables(eng)
         uniq, names = {}, []
         for name, args in rec:
             assert name is not None, "single-GPU step with a collective segment"
             names.append(name)
             if name not in CHECKERS:
                 continue
-            dec = _decode(name, args, blocks)
+            dec = _decode_device_args(eng, tables, name, args, _decode(name, args, blocks))
             uniq.setdefault(_signature(name, dec), (name, dec))
         return uniq, names
     finally:
@@ -190,6 +261,16 @@ def harvest(cfg, dtype_name):
 
 
 # ---------------------------------------------------------------------------------------------------------------- buffers
+def _shift(base, off0, esz, align):
+    """element shift that puts a view's first element base + (s + off0) * esz at its recorded alignment mod 16, on a 64-byte
+    boundary plus that alignment (the whole-pixel stores of the packing and loss kernels require up to 32-byte alignment)"""
+    for mod in (64, 16):
+        for s in range(128):
+            if (base + (s + off0) * esz) % mod == align:
+                return s
+    raise AssertionError(f"no shift gives alignment {align}")
+
+
 class OutBuf:
     """A test-owned buffer laid out like a recorded output view: same pixel strides, ld, channel offset and 16-byte alignment.
     The nc channels of the view's pixels start as NaN, everything else (halo ring, the other channels, TAIL elements) as SENTINEL."""
@@ -204,9 +285,9 @@ class OutBuf:
         hp, wp = h + 2 * halo, w + 2 * halo
         numel = n * hp * wp * ld
         off0 = (halo * wp + halo) * ld + coff
-        self.flat_all = torch.empty(numel + TAIL + 16, dtype=tdt, device=U.DEV)
+        self.flat_all = torch.empty(numel + TAIL + 128, dtype=tdt, device=U.DEV)
         base = self.flat_all.data_ptr()
-        s = next(s for s in range(16) if (base + (s + off0) * esz) % 16 == desc["align"])
+        s = _shift(base, off0, esz, desc["align"])
         self.flat = self.flat_all[s:s + numel + TAIL]
         self.t = self.flat[:numel].view(n, hp, wp, ld)
         self.sl = (slice(None), slice(halo, halo + h), slice(halo, halo + w), slice(coff, coff + nc))
@@ -225,8 +306,7 @@ class OutBuf:
 
     def check_around(self, what):
         got, want = self.flat[self.mask], self._before[self.mask]
-        assert torch.equal(got.view(torch.int16) if got.element_size() == 2 else got.view(torch.int32),
-                           want.view(torch.int16) if want.element_size() == 2 else want.view(torch.int32)), \
+        assert torch.equal(_bits(got), _bits(want)), \
             f"{what}: an element outside the view changed"
         r = self.t[self.sl]
         assert not bool(torch.isnan(r).any()), f"{what}: {int(torch.isnan(r).sum())} elements of the view were not written"
@@ -277,9 +357,9 @@ def in_view(desc, x, dtype, fill_rng):
     hp, wp = h + 2 * halo, w + 2 * halo
     numel = n * hp * wp * ld
     off0 = (halo * wp + halo) * ld + coff
-    flat_all = torch.zeros(numel + TAIL + 16, dtype=U.tdt(dtype), device=U.DEV)
+    flat_all = torch.zeros(numel + TAIL + 128, dtype=U.tdt(dtype), device=U.DEV)
     base = flat_all.data_ptr()
-    s = next(s for s in range(16) if (base + (s + off0) * esz) % 16 == desc["align"])
+    s = _shift(base, off0, esz, desc["align"])
     t = flat_all[s:s + numel].view(n, hp, wp, ld)
     other = torch.as_tensor(U.q(fill_rng.normal(size=(n, h, w, ld)), dtype)).to(U.DEV)
     t[:, halo:halo + h, halo:halo + w, :] = other.to(t.dtype)
@@ -287,14 +367,14 @@ def in_view(desc, x, dtype, fill_rng):
     return flat_all, L.Tensor(base + (s + off0) * esz, ist, rs, ld)
 
 
-def gsrc_in(desc, n, h, w, c, dtype, rng, live=None):
+def gsrc_in(desc, n, h, w, c, dtype, rng, live=None, scale=1.0):
     """gradient source with the recorded kind / slabs / ld / offset: returns (keep-alive, p2p_gsrc, summed f64 values [n,h,w,c]).
-    live [n*h*w, c] (bool): the source is zero where it is False"""
+    live [n*h*w, c] (bool): the source is zero where it is False; scale: standard deviation of the values"""
     pix = n * h * w
     ld, coff, ns, ss = desc["ld"], desc["coff"], max(desc["nslabs"], 1), desc["slab_stride"]
     if desc["kind"] == 2:
         assert ss >= pix * ld, desc
-        data = rng.normal(size=(ns, ss)).astype(np.float32)
+        data = (rng.normal(size=(ns, ss)) * scale).astype(np.float32)
         if live is not None:
             for k in range(ns):
                 data[k, :pix * ld].reshape(pix, ld)[:, coff:coff + c] *= live
@@ -304,7 +384,7 @@ def gsrc_in(desc, n, h, w, c, dtype, rng, live=None):
             vals = vals + data[k, :pix * ld].reshape(pix, ld)[:, coff:coff + c]       # f32, slab order
         ref = vals.astype(np.float64)
     else:
-        data = U.q(rng.normal(size=(pix, ld)), dtype)
+        data = U.q(rng.normal(size=(pix, ld)) * scale, dtype)
         if live is not None:
             data[:, coff:coff + c] *= live
         t = torch.as_tensor(data).to(U.DEV).to(U.tdt(dtype)).contiguous()
@@ -883,12 +963,796 @@ def _head_softmax(name, a, rng):
     return launch
 
 
+# ---------------------------------------------------------------------------------------------------------------- step plumbing
+LOSS_BLOCKS = 256                 # P2P_LOSS_BLOCKS (include/p2pgan.h): one loss partial per workgroup and term
+ADAM_LR = 2e-4                    # (the step size enters through lr_t_dev; any value serves)
+
+
+def _bits(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def _long_k(k):
+    """the bound of a sum of k f32 terms relative to F32_TOL (see _wgrad_family)"""
+    return max(F32_TOL, 4 * np.sqrt(k) * 2.0 ** -24) / F32_TOL
+
+
+def _rel(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.abs(got - want).max() / (np.abs(want).max() + 1e-30))
+
+
+class Buf:
+    """A test-owned flat buffer holding `init` followed by TAIL sentinel elements.  The elements in `written` are what the launch
+    writes (NaN before the launch when `nan`) or updates in place (restored by reset); every other element must be bit-for-bit
+    unchanged after the launch."""
+
+    def __init__(self, init, written=None, nan=False, align=0):
+        init = init.reshape(-1).to(U.DEV)
+        n, esz = init.numel(), init.element_size()
+        self.numel = n
+        fill = SENTINEL if init.is_floating_point() else (0xA5 if init.dtype == torch.uint8 else -7)
+        self.all = torch.empty(n + TAIL + 16, dtype=init.dtype, device=U.DEV)
+        s = next(s for s in range(16) if (self.all.data_ptr() + esz * s) % 16 == align)
+        self.flat = self.all[s:s + n + TAIL]
+        self._init = torch.cat([init, torch.full((TAIL,), fill, dtype=init.dtype, device=U.DEV)])
+        self.written = torch.zeros(n + TAIL, dtype=torch.bool, device=U.DEV)
+        if written is not None:
+            self.written[:n] = written.reshape(-1).to(U.DEV)
+        self.nan = nan
+        self.reset()
+
+    def reset(self):
+        self.flat.copy_(self._init)
+        if self.nan:
+            self.flat[self.written] = float("nan")
+        self._before = self.flat.clone()
+
+    def ptr(self, off=0):
+        return C.c_void_p(self.flat.data_ptr() + off * self.flat.element_size())
+
+    def body(self):
+        return self.flat[:self.numel]
+
+    def check_around(self, what):
+        keep = ~self.written
+        assert torch.equal(_bits(self.flat[keep]), _bits(self._before[keep])), f"{what}: an element outside the written range changed"
+        if self.nan:
+            r = self.flat[self.written]
+            assert not bool(torch.isnan(r).any()), f"{what}: {int(torch.isnan(r).sum())} elements were not written"
+
+
+def _out_all(numel, tdt, align=0):
+    """a flat output every element of which the launch writes"""
+    return Buf(torch.zeros(numel, dtype=tdt), torch.ones(numel, dtype=torch.bool), nan=True, align=align)
+
+
+def _half_out(desc, n, h, w, skip, nc, tdt, esz):
+    """OutBuf for channels [skip, skip + nc) of a recorded view, and the view as the kernel gets it (from channel 0)"""
+    d = dict(desc, coff=desc["coff"] + skip, align=(desc["align"] + skip * esz) % 16)
+    ob = OutBuf(d, n, h, w, nc, tdt, esz)
+    return ob, L.Tensor(ob.view.ptr - skip * esz, ob.view.img_stride, ob.view.row_stride, ob.view.ld)
+
+
+def _vd(h, w, ld, coff=0, halo=0, align=0):
+    """a view description (as _decode makes it) for the direct tests: [h][w] pixels with a halo ring, ld channels"""
+    rs = w + 2 * halo
+    return {"img_stride": (h + 2 * halo) * rs, "row_stride": rs, "ld": ld, "align": align, "coff": coff, "pix": halo * rs + halo}
+
+
+# ---- losses
+def _bce(name, a, rng):
+    """p2p_bce_logits(_pad8): BCE partials of D(real) / D(fake) and the gradients (pix2pix_model.py:44-56)"""
+    dtype, N2, n_real, H, W = a[:5]
+    inv = a[6]
+    pad8 = name == "p2p_bce_logits_pad8"
+    tdt, esz = U.tdt(dtype), _esz(dtype)
+    x = U.q(rng.normal(size=(N2, H, W, 1)) * 3, dtype)
+    keep, lv = in_view(a[5][1], x, dtype, rng)
+    nc = 8 if pad8 else 1
+    dld = OutBuf(a[7][1], N2, H, W, nc, tdt, esz)
+    dlg = OutBuf(a[8][1], N2 - n_real, H, W, nc, tdt, esz) if a[8] is not None else None
+    part = FlatOut(3 * LOSS_BLOCKS, a[9][1])
+    outs = [dld, part] + ([dlg] if dlg else [])
+
+    def go():
+        L.call(name, dtype, N2, n_real, H, W, C.byref(lv), inv, C.byref(dld.view), C.byref(dlg.view) if dlg else None, part.ptr(),
+               U.stream())
+
+    def evaluate():
+        xd = x[..., 0].astype(np.float64)
+        s = 1.0 / (1.0 + np.exp(-xd))
+        sp = np.maximum(xd, 0) + np.log1p(np.exp(-np.abs(xd)))           # BCE(0, x); BCE(1, x) = sp - x
+        real = (np.arange(N2) < n_real)[:, None, None]
+        fam = "out " + ("bf16" if dtype == L.BF16 else "f32")
+        got = dld.region()
+        errs = {fam: SL.per_image_err(got[..., 0], np.where(real, s - 1.0, s) * inv)}
+        if pad8:
+            assert (got[..., 1:] == 0).all(), f"{name}: padding channels of dlogits_d are not 0"
+        if dlg is not None:
+            gg = dlg.region()
+            errs[fam] = max(errs[fam], SL.per_image_err(gg[..., 0], (s[n_real:] - 1.0) * inv))
+            if pad8:
+                assert (gg[..., 1:] == 0).all(), f"{name}: padding channels of dlogits_g are not 0"
+        rows = part.values().reshape(3, LOSS_BLOCKS).sum(axis=1)
+        want = [inv * (sp[:n_real] - xd[:n_real]).sum(), inv * sp[n_real:].sum(), inv * (sp[n_real:] - xd[n_real:]).sum()]
+        errs["loss f32"] = max(abs(r - w) / max(abs(w), 1e-30) for r, w in zip(rows, want)) / _long_k(N2 * H * W)
+        return errs
+
+    launch = Launch(outs, go, evaluate)
+    launch.keep = (keep,)
+    return launch
+
+
+def _tanh_fwd(name, a, rng):
+    """p2p_tanh_l1_fwd(_pair): fake = tanh(z) in the activation dtype (pair form: [fake | source] pixels, the source half copied
+    from real_pair), the unrounded f32 copy and the L1 partials against the stored fake"""
+    pair = name == "p2p_tanh_l1_fwd_pair"
+    if pair:
+        dtype, N, H, W = a[:4]
+        Cc, zd, rd, fd, inv, pi, fi = 4, a[4][1], a[5][1], a[6][1], a[7], 8, 9
+    else:
+        dtype, N, H, W, Cc = a[:5]
+        zd, rd, fd, inv, pi, fi = a[5][1], a[6][1], a[7][1], a[8], 9, 10
+    tdt, esz = U.tdt(dtype), _esz(dtype)
+    rc = 8 if pair else Cc
+    z = U.q(rng.normal(size=(N, H, W, Cc)) * 1.5, dtype)
+    real = U.q(rng.uniform(-1, 1, size=(N, H, W, rc)), dtype)
+    keep_z, zv = in_view(zd, z, dtype, rng)
+    keep_r, rv = in_view(rd, real, dtype, rng)
+    fake = OutBuf(fd, N, H, W, rc, tdt, esz)
+    part = FlatOut(LOSS_BLOCKS, a[pi][1])
+    f32 = FlatOut(N * H * W * Cc, a[fi][1]) if a[fi] is not None else None
+    outs = [fake, part] + ([f32] if f32 else [])
+
+    def go():
+        shape = (N, H, W) if pair else (N, H, W, Cc)
+        L.call(name, dtype, *shape, C.byref(zv), C.byref(rv), C.byref(fake.view), inv, part.ptr(), f32.ptr() if f32 else None,
+               U.stream())
+
+    def evaluate():
+        t = np.tanh(z.astype(np.float64))
+        got = fake.region()
+        errs = {"out " + ("bf16" if dtype == L.BF16 else "f32"): SL.per_image_err(got[..., :Cc], t)}
+        if pair:
+            assert np.array_equal(got[..., 4:], real[..., 4:].astype(np.float64)), f"{name}: the source half is not a copy of real_pair's"
+        if f32 is not None:
+            errs["fake f32"] = SL.per_image_err(f32.values().reshape(N, H, W, Cc), t)
+        want = inv * np.abs(real[..., :Cc].astype(np.float64) - got[..., :Cc]).sum()
+        errs["loss f32"] = abs(part.values().sum() - want) / max(abs(want), 1e-30) / _long_k(N * H * W * Cc)
+        return errs
+
+    launch = Launch(outs, go, evaluate)
+    launch.keep = (keep_z, keep_r)
+    return launch
+
+
+def _tanh_bwd(name, a, rng):
+    """p2p_tanh_l1_bwd(_pad8): dz = (g_d + g_extra + l1_scale * sign(fake - real)) * (1 - fake^2); some real values equal fake
+    (sign 0).  The gradient sources are scaled to l1_scale so that the L1 term is visible"""
+    pad8 = name == "p2p_tanh_l1_bwd_pad8"
+    if pad8:
+        dtype, N, H, W = a[:4]
+        Cc, o = 4, 4
+    else:
+        dtype, N, H, W, Cc = a[:5]
+        o = 5
+    fd, rd, gdd, gxd, l1, dzd = a[o][1], a[o + 1][1], a[o + 2], a[o + 3], a[o + 4], a[o + 5][1]
+    tdt, esz = U.tdt(dtype), _esz(dtype)
+    f = U.q(np.tanh(rng.normal(size=(N, H, W, Cc)) * 1.5), dtype)
+    r = U.q(rng.uniform(-1, 1, size=(N, H, W, Cc)), dtype)
+    eq = rng.random(size=f.shape) < 0.15
+    r[eq] = f[eq]
+    keep_f, fv = in_view(fd, f, dtype, rng)
+    keep_r, rv = in_view(rd, r, dtype, rng)
+    sc = abs(l1) if l1 else 1.0
+    k1, g1, r1 = gsrc_in(gdd[1], N, H, W, Cc, dtype, rng, scale=sc) if gdd is not None else (None, None, 0.0)
+    k2, g2, r2 = gsrc_in(gxd[1], N, H, W, Cc, dtype, rng, scale=sc) if gxd is not None else (None, None, 0.0)
+    dz = OutBuf(dzd, N, H, W, 8 if pad8 else Cc, tdt, esz)
+
+    def go():
+        shape = (N, H, W) if pad8 else (N, H, W, Cc)
+        L.call(name, dtype, *shape, C.byref(fv), C.byref(rv), C.byref(g1) if g1 else None, C.byref(g2) if g2 else None, l1,
+               C.byref(dz.view), U.stream())
+
+    def evaluate():
+        fd64 = f.astype(np.float64)
+        want = (r1 + r2 + l1 * np.sign(fd64 - r)) * (1.0 - fd64 ** 2)
+        got = dz.region()
+        if pad8:
+            assert (got[..., 4:] == 0).all(), f"{name}: padding channels of dz are not 0"
+        return {"out " + ("bf16" if dtype == L.BF16 else "f32"): SL.per_image_err(got[..., :Cc], want)}
+
+    launch = Launch([dz], go, evaluate)
+    launch.keep = (keep_f, keep_r, k1, k2)
+    return launch
+
+
+def _partials_sum(name, a, rng):
+    """p2p_loss_partials_sum: out[k] = sum of the LOSS_BLOCKS partials of row k"""
+    K = a[1]
+    part = (rng.random(size=K * LOSS_BLOCKS) * 2 + 0.01).astype(np.float32)
+    pd = U.dev(part)
+    out = FlatOut(K, a[2][1])
+
+    def go():
+        L.call(name, U.ptr(pd), K, out.ptr(), U.stream())
+
+    def evaluate():
+        want = part.astype(np.float64).reshape(K, LOSS_BLOCKS).sum(axis=1)
+        return {"loss f32": float((np.abs(out.values() - want) / want).max()) / _long_k(LOSS_BLOCKS)}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (pd,)
+    return launch
+
+
+def _finish_losses(name, a, rng):
+    """p2p_finish_losses against its formula (include/p2pgan.h): [g_total, g_adv, g_l1, g_aux, d_total, d_real, d_fake]"""
+    aux, l1s, lam1, lamx = a[1], a[2], a[3], a[4]
+    slots = (rng.random(size=8) + 0.1).astype(np.float32)
+    sd = U.dev(slots)
+    out = FlatOut(7, a[5][1])
+
+    def go():
+        L.call(name, U.ptr(sd), aux, l1s, lam1, lamx, out.ptr(), U.stream())
+
+    def evaluate():
+        s = slots.astype(np.float64)
+        ax = s[aux] if aux >= 0 else 0.0
+        want = [s[2] + lam1 * s[l1s] + lamx * ax, s[2], s[l1s], ax, s[0] + s[1], s[0], s[1]]
+        got = out.values()
+        for i in (1, 2, 3, 5, 6):
+            assert got[i] == want[i], f"{name}: out[{i}] = {got[i]} is not slot value {want[i]} (aux_slot {aux}, l1_slot {l1s})"
+        return {"loss f32": max(abs(got[i] - want[i]) / abs(want[i]) for i in (0, 4))}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (sd,)
+    return launch
+
+
+def _raw_hists(rng, N):
+    x = rng.random(size=(N, 3 * 64 * 64)) ** 3 * 50
+    x[rng.random(size=x.shape) < 0.2] = 0.0
+    return x.astype(np.float32)
+
+
+def _hellinger_fwd(name, a, rng):
+    """p2p_hellinger_fwd: per-image totals of both raw histograms, per-image and summed Hellinger sums of squares"""
+    N = a[2]
+    E = 3 * 64 * 64
+    ht, hp = _raw_hists(rng, N), _raw_hists(rng, N)
+    htd, hpd = U.dev(ht.reshape(-1)), U.dev(hp.reshape(-1))
+    tt, tp, sqp, sq = FlatOut(N, a[3][1]), FlatOut(N, a[4][1]), FlatOut(N, a[5][1]), FlatOut(1, a[6][1])
+
+    def go():
+        L.call(name, U.ptr(htd), U.ptr(hpd), N, tt.ptr(), tp.ptr(), sqp.ptr(), sq.ptr(), U.stream())
+
+    def evaluate():
+        T, Pp = ht.astype(np.float64).sum(axis=1), hp.astype(np.float64).sum(axis=1)
+        s = ((np.sqrt(hp / Pp[:, None]) - np.sqrt(ht / T[:, None])) ** 2).sum(axis=1)
+        e = max(float((np.abs(tt.values() - T) / T).max()), float((np.abs(tp.values() - Pp) / Pp).max()),
+                float((np.abs(sqp.values() - s) / s).max())) / _long_k(E)
+        return {"loss f32": max(e, abs(sq.values()[0] - s.sum()) / s.sum() / _long_k(E * N))}
+
+    launch = Launch([tt, tp, sqp, sq], go, evaluate)
+    launch.keep = (htd, hpd)
+    return launch
+
+
+def _hellinger_finish(name, a, rng):
+    """p2p_hellinger_finish: loss = sqrt(sq_sum) / sqrt(2) * inv_global_batch"""
+    inv = a[1]
+    sq = float(np.float32(rng.random() * 3 + 0.5))
+    sqd = U.dev(np.array([sq, 0, 0, 0], np.float32))
+    out = FlatOut(1, a[2][1])
+
+    def go():
+        L.call(name, U.ptr(sqd), inv, out.ptr(), U.stream())
+
+    def evaluate():
+        want = np.sqrt(sq) / np.sqrt(2.0) * inv
+        return {"loss f32": abs(out.values()[0] - want) / want}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (sqd,)
+    return launch
+
+
+def _hist_normalize(name, a, rng):
+    """p2p_hist_normalize: raw [N][3][64][64] -> [N][64][64][3] / per-image total"""
+    N = a[1]
+    raw = _raw_hists(rng, N)
+    rd = U.dev(raw.reshape(-1))
+    out = FlatOut(N * 3 * 64 * 64, a[2][1])
+
+    def go():
+        L.call(name, U.ptr(rd), N, out.ptr(), U.stream())
+
+    def evaluate():
+        return {"histogram": SL.per_image_err(out.values().reshape(N, 64, 64, 3), _raw_to_norm(raw, N))}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (rd,)
+    return launch
+
+
+# ---- reductions
+def _colsum(name, a, rng):
+    """p2p_colsum: out[c] = scale * sum_r part[r][c]"""
+    rows, cols, scale = a[1], a[2], a[3]
+    part = rng.normal(0.3, 1.0, size=(rows, cols)).astype(np.float32)
+    pd = U.dev(part.reshape(-1))
+    out = FlatOut(cols, a[4][1])
+
+    def go():
+        L.call(name, U.ptr(pd), rows, cols, scale, out.ptr(), U.stream())
+
+    def evaluate():
+        return {"colsum f32": _rel(out.values(), scale * part.astype(np.float64).sum(axis=0)) / _long_k(rows)}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (pd,)
+    return launch
+
+
+def _view_colsum(name, a, rng):
+    """p2p_view_colsum: column sums over every pixel of a view (bias gradients), with its workspace"""
+    dtype, N, H, W, Cc = a[:5]
+    x = U.q(rng.normal(0.3, 1.0, size=(N, H, W, Cc)), dtype)
+    keep, vv = in_view(a[5][1], x, dtype, rng)
+    out = FlatOut(Cc, a[6][1])
+    need = L.lib().p2p_view_colsum_workspace_bytes(dtype, N, H, W, Cc, C.byref(vv)) // 4
+    ws = torch.full((max(need, 16),), float("nan"), dtype=torch.float32, device=U.DEV)
+
+    def go():
+        L.call(name, dtype, N, H, W, Cc, C.byref(vv), out.ptr(), U.ptr(ws), U.stream())
+
+    def evaluate():
+        return {"colsum f32": _rel(out.values(), x.astype(np.float64).sum(axis=(0, 1, 2))) / _long_k(N * H * W)}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (keep, ws)
+    return launch
+
+
+def _colsum_batched(name, a, rng):
+    """p2p_colsum_batched: task {part_off, rows, cols, out_off} sums a [rows][cols] block into out + out_off; the rest of the
+    output buffer (the recorded one is the generator's flat gradient buffer) keeps its values"""
+    tasks = [tuple(t) for t in a[1][1]]
+    ntasks, maxc = a[2], a[3]
+    numel = a[4][2] - a[4][3]
+    assert len(tasks) == ntasks and maxc == max(t[2] for t in tasks), (ntasks, maxc, tasks)
+    part = rng.normal(0.3, 1.0, size=max(po + r * c for po, r, c, _ in tasks)).astype(np.float32)
+    pd = U.dev(part)
+    written = torch.zeros(numel, dtype=torch.bool)
+    for _, _, c, oo in tasks:
+        written[oo:oo + c] = True
+    out = Buf(torch.full((numel,), SENTINEL), written, nan=True)
+    table = torch.tensor(tasks, dtype=torch.int32, device=U.DEV)
+
+    def go():
+        L.call(name, U.ptr(pd), U.ptr(table), ntasks, maxc, out.ptr(), U.stream())
+
+    def evaluate():
+        got = out.body().double().cpu().numpy()
+        e = 0.0
+        for po, r, c, oo in tasks:
+            want = part[po:po + r * c].astype(np.float64).reshape(r, c).sum(axis=0)
+            e = max(e, _rel(got[oo:oo + c], want) / _long_k(r))
+        return {"colsum f32": e}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (pd, table)
+    return launch
+
+
+# ---- packing (exact: the activation-dtype rounding of the input, ties to even)
+def _exact(got, want, what):
+    assert np.array_equal(np.asarray(got, np.float64), np.asarray(want, np.float64)), f"{what}: not the dtype rounding of the input"
+
+
+def _pack_pair(name, a, rng):
+    """p2p_pack_pair(_idx): v_src = [source | 0], v_c6 = the same pixel, v_dreal = [target | source] ([target source 0 ..] for
+    indices), v_dfake = its source half ([0 source 0 ..] for indices)"""
+    dtype, N, H, W = a[:4]
+    tdt, esz = U.tdt(dtype), _esz(dtype)
+    idx = name == "p2p_pack_pair_idx"
+    if idx:
+        src = rng.integers(0, 256, size=(N, H, W)).astype(np.int32)
+        tgt = rng.integers(0, 256, size=(N, H, W)).astype(np.int32)
+        sd, td = U.dev(src, torch.int32), U.dev(tgt, torch.int32)
+    else:
+        src = rng.uniform(-1, 1, size=(N, H, W, 4)).astype(np.float32)
+        tgt = rng.uniform(-1, 1, size=(N, H, W, 4)).astype(np.float32)
+        sd, td = U.dev(src), U.dev(tgt)
+    vs = OutBuf(a[6][1], N, H, W, 8, tdt, esz)
+    vc = OutBuf(a[7][1], N, H, W, 8, tdt, esz) if a[7] is not None else None
+    vr = OutBuf(a[8][1], N, H, W, 8, tdt, esz)
+    vf = vf_view = None
+    if a[9] is not None:
+        if idx:
+            vf = OutBuf(a[9][1], N, H, W, 8, tdt, esz)
+            vf_view = vf.view
+        else:
+            vf, vf_view = _half_out(a[9][1], N, H, W, 4, 4, tdt, esz)
+    outs = [o for o in (vs, vc, vr, vf) if o is not None]
+
+    def go():
+        L.call(name, dtype, N, H, W, U.ptr(sd), U.ptr(td), C.byref(vs.view), C.byref(vc.view) if vc else None, C.byref(vr.view),
+               C.byref(vf_view) if vf else None, U.stream())
+
+    def evaluate():
+        z = np.zeros((N, H, W, 1))
+        if idx:
+            s, t = src[..., None].astype(np.float64), tgt[..., None].astype(np.float64)
+            want_s = np.concatenate([s] + [z] * 7, -1)
+            want_r = np.concatenate([t, s] + [z] * 6, -1)
+            want_f = np.concatenate([z, s] + [z] * 6, -1)
+        else:
+            s, t = U.q(src, dtype), U.q(tgt, dtype)
+            want_s = np.concatenate([s, np.zeros_like(s)], -1)
+            want_r = np.concatenate([t, s], -1)
+            want_f = s
+        _exact(vs.region(), want_s, f"{name} v_src")
+        if vc is not None:
+            _exact(vc.region(), want_s, f"{name} v_c6")
+        _exact(vr.region(), want_r, f"{name} v_dreal")
+        if vf is not None:
+            _exact(vf.region(), want_f, f"{name} v_dfake")
+        return {"exact": 0.0}
+
+    launch = Launch(outs, go, evaluate)
+    launch.keep = (sd, td)
+    return launch
+
+
+def _pack_input(name, a, rng):
+    """p2p_pack_input(_multi): a dense f32 or int32 [N][H][W][C] batch into one or up to four views"""
+    dtype, N, H, W, Cc = a[:5]
+    is_int = a[6]
+    tdt, esz = U.tdt(dtype), _esz(dtype)
+    if is_int:
+        src = rng.integers(-300, 300, size=(N, H, W, Cc)).astype(np.int32)
+        sd = U.dev(src, torch.int32)
+        want = U.q(src.astype(np.float32), dtype)
+    else:
+        src = rng.uniform(-1, 1, size=(N, H, W, Cc)).astype(np.float32)
+        sd = U.dev(src)
+        want = U.q(src, dtype)
+    descs = [dict(d) for d in a[7][1]] if name == "p2p_pack_input_multi" else [a[7][1]]
+    outs = [OutBuf(d, N, H, W, Cc, tdt, esz) for d in descs]
+    arr = (L.Tensor * len(outs))(*[o.view for o in outs])
+
+    def go():
+        if name == "p2p_pack_input_multi":
+            L.call(name, dtype, N, H, W, Cc, U.ptr(sd), is_int, arr, len(outs), U.stream())
+        else:
+            L.call(name, dtype, N, H, W, Cc, U.ptr(sd), is_int, C.byref(outs[0].view), U.stream())
+
+    def evaluate():
+        for k, o in enumerate(outs):
+            _exact(o.region(), want, f"{name} view {k}")
+        return {"exact": 0.0}
+
+    launch = Launch(outs, go, evaluate)
+    launch.keep = (sd, arr)
+    return launch
+
+
+def _unpack(name, a, rng):
+    """p2p_unpack: a view -> dense f32 [N][H][W][C]"""
+    dtype, N, H, W, Cc = a[:5]
+    x = U.q(rng.normal(size=(N, H, W, Cc)), dtype)
+    keep, v = in_view(a[5][1], x, dtype, rng)
+    out = FlatOut(N * H * W * Cc, a[6][1])
+
+    def go():
+        L.call(name, dtype, N, H, W, Cc, C.byref(v), out.ptr(), U.stream())
+
+    def evaluate():
+        _exact(out.values().reshape(N, H, W, Cc), x, name)
+        return {"exact": 0.0}
+
+    launch = Launch([out], go, evaluate)
+    launch.keep = (keep,)
+    return launch
+
+
+def _copy_ref(w, cg, cd, rows, cols, transpose, tdt):
+    """operand copy [16][rows][cols] of the master W[16][Cg][Cd] (transposed: [16][Cd][Cg]) in tdt, zero outside the real block"""
+    w3 = w.reshape(16, cg, cd)
+    if transpose:
+        w3 = w3.transpose(1, 2)
+    out = torch.zeros((16, rows, cols), dtype=tdt, device=w.device)
+    r, c = min(rows, w3.shape[1]), min(cols, w3.shape[2])
+    out[:, :r, :c] = w3[:, :r, :c].to(tdt)
+    return out.reshape(-1)
+
+
+def _copy_buf(rows, cols, tdt):
+    n = 16 * rows * cols
+    return Buf(torch.zeros(n, dtype=tdt), torch.ones(n, dtype=torch.bool), nan=True)
+
+
+def _check_copy(buf, want, what):
+    assert torch.equal(_bits(buf.body()), _bits(want)), f"{what}: not the dtype rounding of the master (or padding not 0)"
+
+
+def _weight_prep(name, a, rng):
+    """p2p_weight_prep(_pad): wn [16][wn_rows][wn_cols] and / or wt [16][wt_rows][wt_cols] from the f32 master"""
+    dtype, cg, cd = a[0], a[2], a[3]
+    if name == "p2p_weight_prep":
+        shapes = ((cg, cd) if a[4] else None, (cd, cg) if a[5] else None)
+    else:
+        shapes = ((a[5], a[6]) if a[4] else None, (a[8], a[9]) if a[7] else None)
+    tdt = U.tdt(dtype)
+    w = torch.as_tensor(rng.normal(scale=0.05, size=16 * cg * cd).astype(np.float32)).to(U.DEV)
+    bufs = [_copy_buf(*s, tdt) if s else None for s in shapes]
+
+    def go():
+        pn, pt = (b.ptr() if b else None for b in bufs)
+        if name == "p2p_weight_prep":
+            L.call(name, dtype, U.ptr(w), cg, cd, pn, pt, U.stream())
+        else:
+            L.call(name, dtype, U.ptr(w), cg, cd, pn, *(shapes[0] or (0, 0)), pt, *(shapes[1] or (0, 0)), U.stream())
+
+    def evaluate():
+        for k, (b, s) in enumerate(zip(bufs, shapes)):
+            if b is not None:
+                _check_copy(b, _copy_ref(w, cg, cd, s[0], s[1], k == 1, tdt), f"{name} {'wt' if k else 'wn'}")
+        return {"exact": 0.0}
+
+    launch = Launch([b for b in bufs if b], go, evaluate)
+    launch.keep = (w,)
+    return launch
+
+
+def _task_table(tasks, masters, bufs):
+    """a fresh p2p_prep_task table pointing at test-owned buffers (tasks as decoded by _decode_tasks)"""
+    arr = (L.PrepTask * len(tasks))()
+    for k, (t, wp, (bn, bt)) in enumerate(zip(tasks, masters, bufs)):
+        cg, cd, wnr, wnc, wtr, wtc, _, _, tg, td, first = t[:11]
+        e = arr[k]
+        e.w = wp
+        e.wn = bn.flat.data_ptr() if bn else None
+        e.wt = bt.flat.data_ptr() if bt else None
+        e.Cg, e.Cd, e.wn_rows, e.wn_cols, e.wt_rows, e.wt_cols = cg, cd, wnr, wnc, wtr, wtc
+        e.tiles_g, e.tiles_d, e.first_block = tg, td, first
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(U.DEV)
+
+
+def _task_copies(t, tdt):
+    cg, cd, wnr, wnc, wtr, wtc, has_wn, has_wt = t[:8]
+    return (_copy_buf(wnr, wnc, tdt) if has_wn else None, _copy_buf(wtr, wtc, tdt) if has_wt else None)
+
+
+def _check_task_copies(name, tasks, masters, bufs, tdt):
+    for k, (t, w, (bn, bt)) in enumerate(zip(tasks, masters, bufs)):
+        cg, cd, wnr, wnc, wtr, wtc = t[:6]
+        if bn is not None:
+            _check_copy(bn, _copy_ref(w, cg, cd, wnr, wnc, False, tdt), f"{name} task {k} ({cg}x{cd}) wn")
+        if bt is not None:
+            _check_copy(bt, _copy_ref(w, cg, cd, wtr, wtc, True, tdt), f"{name} task {k} ({cg}x{cd}) wt")
+
+
+def _weight_prep_batched(name, a, rng):
+    """p2p_weight_prep_batched: every task's copies from a fresh master"""
+    dtype, tasks, ntasks, total = a[0], a[1][1], a[2], a[3]
+    tdt = U.tdt(dtype)
+    masters = [torch.as_tensor(rng.normal(scale=0.05, size=16 * t[0] * t[1]).astype(np.float32)).to(U.DEV) for t in tasks]
+    bufs = [_task_copies(t, tdt) for t in tasks]
+    table = _task_table(tasks, [m.data_ptr() for m in masters], bufs)
+
+    def go():
+        L.call(name, dtype, U.ptr(table), ntasks, total, U.stream())
+
+    def evaluate():
+        _check_task_copies(name, tasks, masters, bufs, tdt)
+        return {"exact": 0.0}
+
+    launch = Launch([b for pair in bufs for b in pair if b], go, evaluate)
+    launch.keep = (masters, table)
+    return launch
+
+
+# ---- optimizer
+def _adam_state(numel, ranges, t, seed):
+    """flat params / grads / m / v of `numel` f32 elements: SENTINEL everywhere but in `ranges`, which hold masters, gradients
+    spread over 1e-8..1 with random signs and some exact zeros, and (t > 1) the moments of earlier steps.  Generated on the device."""
+    gen = torch.Generator(device=U.DEV)
+    gen.manual_seed(seed)
+
+    def rn(k):
+        return torch.randn(k, generator=gen, device=U.DEV, dtype=torch.float64)
+
+    def ru(k):
+        return torch.rand(k, generator=gen, device=U.DEV, dtype=torch.float64)
+
+    def spread(k):
+        return torch.sign(rn(k)) * 10.0 ** (-8.0 * ru(k))
+
+    p, g, m, v = (torch.full((numel,), SENTINEL, dtype=torch.float32, device=U.DEV) for _ in range(4))
+    written = torch.zeros(numel, dtype=torch.bool, device=U.DEV)
+    for lo, hi in ranges:
+        k = hi - lo
+        p[lo:hi] = (rn(k) * 0.02).float()
+        gg = spread(k)
+        gg[ru(k) < 0.03] = 0.0
+        g[lo:hi] = gg.float()
+        if t > 1:
+            prev = spread(k)
+            m[lo:hi] = (0.5 * prev).float()
+            v[lo:hi] = (1e-3 * prev ** 2 * (1.0 + ru(k))).float()
+        else:
+            m[lo:hi] = 0.0
+            v[lo:hi] = 0.0
+        written[lo:hi] = True
+    return p, g, m, v, written
+
+
+def _adam_errs(p, m, v, p0, g, m0, v0, t, b1, b2, eps, sel=None):
+    """normalised errors of an f32 Adam step against the f64 Keras step (1.0 = the bound of test_adam_matches_keras_formulation:
+    p rtol 1e-6 / atol 1e-7, v rtol 5e-5; m rtol 1e-6 of its inputs' scale)"""
+    if sel is not None:
+        p, m, v, p0, g, m0, v0 = (x[sel] for x in (p, m, v, p0, g, m0, v0))
+    p0, g, m0, v0 = (x.double() for x in (p0, g, m0, v0))
+    pr, mr, vr = SL.keras_adam(p0, g, m0, v0, t, ADAM_LR, b1, b2, eps)
+    ep = ((p.double() - pr).abs() / (1e-6 * pr.abs() + 1e-7)).max()
+    em = ((m.double() - mr).abs() / (1e-6 * torch.maximum(mr.abs(), torch.maximum(m0.abs(), g.abs())) + 1e-30)).max()
+    ev = ((v.double() - vr).abs() / (5e-5 * vr.abs() + 1e-30)).max()
+    return {"adam p": float(ep), "adam m": float(em), "adam v": float(ev)}
+
+
+def _lr_t(t, b1, b2):
+    return float(np.float32(ADAM_LR * np.sqrt(1.0 - float(b2) ** t) / (1.0 - float(b1) ** t)))
+
+
+def _adam_tick(name, a, rng, t=1):
+    """p2p_adam_tick: t_dev += 1, lr_t_dev = lr sqrt(1 - b2^t) / (1 - b1^t)"""
+    lr, b1, b2 = a[2], a[3], a[4]
+    tb = Buf(torch.tensor([t - 1], dtype=torch.int32), torch.ones(1, dtype=torch.bool))
+    lb = Buf(torch.zeros(1), torch.ones(1, dtype=torch.bool), nan=True)
+
+    def go():
+        L.call(name, tb.ptr(), lb.ptr(), lr, b1, b2, U.stream())
+
+    def evaluate():
+        assert int(tb.body()[0]) == t, f"{name}: t_dev {int(tb.body()[0])} after a tick from {t - 1}"
+        want = lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+        return {"adam lr_t": abs(float(lb.body()[0]) - want) / want / 1e-6}
+
+    return Launch([tb, lb], go, evaluate)
+
+
+def _adam_flat(name, a, rng, t=1):
+    """p2p_adam_flat(_dev) on [off, off + n) of a flat buffer laid out like the recorded store: every other element (the rest of
+    the store, the small-tensor tail or the kernels in front of it) keeps its sentinel"""
+    if name == "p2p_adam_flat_dev":
+        _, sid, numel, off = a[0]
+        n, b1, b2, eps, gs = a[4], a[6], a[7], a[8], a[9]
+    else:
+        numel, off = a[4] + 64, 32                # (direct test: a region inside a larger buffer)
+        n, lr, b1, b2, eps, gs = a[4], a[6], a[7], a[8], a[9], a[10]
+        assert lr == ADAM_LR, lr
+    p, g, m, v, written = _adam_state(numel, [(off, off + n)], t, seed=int(rng.integers(1 << 30)))
+    pb, mb, vb = (Buf(x, written) for x in (p, m, v))
+    gb = Buf(g)
+    lrd = U.dev(np.array([_lr_t(t, b1, b2), 0, 0, 0], np.float32))
+
+    def go():
+        if name == "p2p_adam_flat_dev":
+            L.call(name, pb.ptr(off), gb.ptr(off), mb.ptr(off), vb.ptr(off), n, U.ptr(lrd), b1, b2, eps, gs, U.stream())
+        else:
+            L.call(name, pb.ptr(off), gb.ptr(off), mb.ptr(off), vb.ptr(off), n, t, ADAM_LR, b1, b2, eps, gs, U.stream())
+
+    def evaluate():
+        sl = slice(off, off + n)
+        return _adam_errs(pb.body()[sl], mb.body()[sl], vb.body()[sl], p[sl], g[sl] * gs, m[sl], v[sl], t, b1, b2, eps)
+
+    launch = Launch([pb, mb, vb, gb], go, evaluate)
+    launch.keep = (lrd,)
+    return launch
+
+
+def _adam_prep(name, a, rng, t=1):
+    """p2p_adam_prep_batched: the masters at their recorded offsets inside a params / grads / m / v store that is otherwise
+    sentinel (the other part's kernels and the small-tensor tail of p2p_adam_flat_dev included); operand copies = the dtype
+    rounding of the new master, zero padding"""
+    dtype, n_elems, tasks, ntasks, total = a[0], a[1], a[2][1], a[3], a[4]
+    _, sid, numel = a[5]
+    b1, b2, eps = a[10], a[11], a[12]
+    tdt = U.tdt(dtype)
+    ranges = [(t_[12], t_[12] + 16 * t_[0] * t_[1]) for t_ in tasks]
+    assert all(t_[11] == sid for t_ in tasks), f"{name}: a task's master lies outside the store passed as params"
+    assert sum(hi - lo for lo, hi in ranges) == n_elems, (n_elems, ranges)
+    p, g, m, v, written = _adam_state(numel, ranges, t, seed=int(rng.integers(1 << 30)))
+    pb, mb, vb = (Buf(x, written) for x in (p, m, v))
+    gb = Buf(g)
+    bufs = [_task_copies(t_, tdt) for t_ in tasks]
+    table = _task_table(tasks, [pb.flat.data_ptr() + 4 * lo for lo, _ in ranges], bufs)
+    lrd = U.dev(np.array([_lr_t(t, b1, b2), 0, 0, 0], np.float32))
+
+    def go():
+        L.call(name, dtype, n_elems, U.ptr(table), ntasks, total, pb.ptr(), gb.ptr(), mb.ptr(), vb.ptr(), U.ptr(lrd), b1, b2, eps,
+               U.stream())
+
+    def evaluate():
+        errs = _adam_errs(pb.body(), mb.body(), vb.body(), p, g, m, v, t, b1, b2, eps, sel=written)
+        _check_task_copies(name, tasks, [pb.body()[lo:hi] for lo, hi in ranges], bufs, tdt)
+        return errs
+
+    launch = Launch([pb, mb, vb, gb] + [b for pair in bufs for b in pair if b], go, evaluate)
+    launch.keep = (table, lrd)
+    return launch
+
+
+# ---- dropout RNG
+def _dropout(name, a, rng):
+    """p2p_dropout_mask(_dev) bit for bit against tests/step_launches.dropout_mask, at a device counter that is not 0"""
+    n, seed = a[1], a[2]
+    cb = None
+    if name == "p2p_dropout_mask_dev":
+        cval = 3
+        salt, eoff = a[4], a[5]
+        cb = Buf(torch.tensor([cval], dtype=torch.int64))
+        counter, group0 = cval * 16 + salt, eoff // 8
+    else:
+        counter, group0 = a[3], 0
+    mb = Buf(torch.full((n,), 0xA5, dtype=torch.uint8), torch.ones(n, dtype=torch.bool))
+
+    def go():
+        if cb is not None:
+            L.call(name, mb.ptr(), n, seed, cb.ptr(), salt, eoff, U.stream())
+        else:
+            L.call(name, mb.ptr(), n, seed, counter, U.stream())
+
+    def evaluate():
+        got = mb.body().cpu().numpy()
+        want = SL.dropout_mask(n, seed, counter, group0)
+        bad = int((got != want).sum())
+        assert bad == 0, f"{name}: {bad} of {n} mask bytes differ from the generator (n {n}, seed {seed}, counter {counter})"
+        return {"exact": 0.0}
+
+    return Launch([mb] + ([cb] if cb else []), go, evaluate)
+
+
+def _counter_add(name, a, rng):
+    """p2p_counter_add: counter += inc, exactly, in 64 bits"""
+    inc = a[1]
+    c0 = (1 << 40) + 12345
+    cb = Buf(torch.tensor([c0], dtype=torch.int64), torch.ones(1, dtype=torch.bool))
+
+    def go():
+        L.call(name, cb.ptr(), inc, U.stream())
+
+    def evaluate():
+        assert int(cb.body()[0]) == c0 + inc, f"{name}: {int(cb.body()[0])} != {c0} + {inc}"
+        return {"exact": 0.0}
+
+    return Launch([cb], go, evaluate)
+
+
+ADAM_STEPS = (1, 3)         # re-issued at t = 1 (m = v = 0) and at t = 3
+VARIANTS = {n: [{"t": t} for t in ADAM_STEPS] for n in ("p2p_adam_tick", "p2p_adam_flat", "p2p_adam_flat_dev", "p2p_adam_prep_batched")}
+
+
 CHECKERS = {n: _conv_family for n in ("p2p_igemm", "p2p_igemm_norm_act", "p2p_conv_strip", "p2p_igemm_edge", "p2p_conv_fewin",
                                       "p2p_conv_fewin_actbwd", "p2p_conv_fewout")}
 CHECKERS.update({n: _wgrad_family for n in ("p2p_wgemm", "p2p_wgemm_edge", "p2p_wgrad_small")})
 CHECKERS.update({"p2p_norm_act_fwd": _norm_fwd, "p2p_norm_act_fwd_tail": _norm_fwd, "p2p_act_bwd": _act_bwd,
                  "p2p_norm_act_bwd": _norm_bwd, "p2p_rgbuv_points": _points, "p2p_rgbuv_hist_fwd3": _hist_fwd3,
                  "p2p_rgbuv_hist_hellinger_bwd3": _hist_bwd3, "p2p_head_dgrad": _head_dgrad, "p2p_head_softmax_cce": _head_softmax})
+CHECKERS.update({"p2p_bce_logits": _bce, "p2p_bce_logits_pad8": _bce, "p2p_tanh_l1_fwd": _tanh_fwd, "p2p_tanh_l1_fwd_pair": _tanh_fwd,
+                 "p2p_tanh_l1_bwd": _tanh_bwd, "p2p_tanh_l1_bwd_pad8": _tanh_bwd, "p2p_loss_partials_sum": _partials_sum,
+                 "p2p_finish_losses": _finish_losses, "p2p_hellinger_fwd": _hellinger_fwd, "p2p_hellinger_finish": _hellinger_finish,
+                 "p2p_hist_normalize": _hist_normalize, "p2p_colsum": _colsum, "p2p_view_colsum": _view_colsum,
+                 "p2p_colsum_batched": _colsum_batched, "p2p_pack_pair": _pack_pair, "p2p_pack_pair_idx": _pack_pair,
+                 "p2p_pack_input": _pack_input, "p2p_pack_input_multi": _pack_input, "p2p_unpack": _unpack,
+                 "p2p_weight_prep": _weight_prep, "p2p_weight_prep_pad": _weight_prep, "p2p_weight_prep_batched": _weight_prep_batched,
+                 "p2p_adam_tick": _adam_tick, "p2p_adam_flat": _adam_flat, "p2p_adam_flat_dev": _adam_flat,
+                 "p2p_adam_prep_batched": _adam_prep, "p2p_dropout_mask": _dropout, "p2p_dropout_mask_dev": _dropout,
+                 "p2p_counter_add": _counter_add})
 
 
 def _tol(family, dtype):
@@ -900,6 +1764,10 @@ def _tol(family, dtype):
         return 1e-4                                     # test_hist_indexed_gpu.py: f32 logf / division against f64
     if family == "hist grad":
         return 2e-3                                     # test_hist_indexed_gpu.py: gradient spanning ~6 decades (1/(x+1e-6))
+    if family.startswith("adam"):
+        return 1.0              # (normalised by the Keras bounds in _adam_errs / _adam_tick)
+    if family in ("fake f32", "colsum f32", "exact"):
+        return F32_TOL          # (f32 tanh against f64; column sums already scaled by the long-K bound; exact: 0)
     if family in ("loss f32", "dbias f32", "points"):
         return F32_TOL          # (loss / bias sums already scaled by the long-K bound; points: exact)
     if family == "norm out":
@@ -914,8 +1782,16 @@ def _tol(family, dtype):
 
 
 def _reissue(name, dec, seed):
+    errs = {}
+    for kw in VARIANTS.get(name, [{}]):
+        for fam, e in _reissue_one(name, dec, seed, kw).items():
+            errs[fam] = max(errs.get(fam, 0.0), e)
+    return errs
+
+
+def _reissue_one(name, dec, seed, kw):
     rng = np.random.default_rng(seed)
-    launch = CHECKERS[name](name, dec, rng)
+    launch = CHECKERS[name](name, dec, rng, **kw)
     launch.go()
     torch.cuda.synchronize()
     for o in launch.outs:
@@ -929,16 +1805,22 @@ def _reissue(name, dec, seed):
     for t, f in zip(getattr(launch, "fixed", ()), fixed):
         assert torch.equal(t, f), f"{name}: second launch differs"
     for o, f in zip(launch.outs, first):
-        assert torch.equal(o.flat.view(torch.int16) if o.flat.element_size() == 2 else o.flat.view(torch.int32),
-                           f.view(torch.int16) if f.element_size() == 2 else f.view(torch.int32)), f"{name}: second launch differs"
+        assert torch.equal(_bits(o.flat), _bits(f)), f"{name}: second launch differs"
     errs = launch.evaluate()
     del launch
     return errs
 
 
-@pytest.mark.parametrize("cfg,dtype_name", CONFIGS, ids=[f"{c}-{d}" for c, d in CONFIGS])
-def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name):
-    uniq, names = harvest(cfg, dtype_name)
+STEP_CASES = [(c, d, None) for c, d in CONFIGS] + [("c2", "bf16", True)]
+
+
+@pytest.mark.parametrize("cfg,dtype_name,fuse", STEP_CASES, ids=[f"{c}-{d}" + ("-fused-adam" if f else "") for c, d, f in STEP_CASES])
+def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name, fuse):
+    """fuse: also the step with Adam and the operand copies in one launch per part (p2p_adam_prep_batched on the G_head / G_rest /
+    D tables), the engine's other Adam path"""
+    uniq, names = harvest(cfg, dtype_name, fuse)
+    if fuse:
+        assert "p2p_adam_prep_batched" in names, "the fused-Adam step issues no p2p_adam_prep_batched"
     unknown = sorted({n for n in names if n not in CHECKERS and n not in OUT_OF_SCOPE})
     assert not unknown, f"{cfg}: entry points neither re-issued nor listed as out of scope: {unknown}"
     dtype = L.BF16 if dtype_name == "bf16" else L.F32
@@ -956,7 +1838,7 @@ def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name):
             if not e < _tol(fam, dtype):
                 failures.append(f"{name} {[d for d in dec if not isinstance(d, tuple)][:12]}: {fam} error {e:.3g} >= {_tol(fam, dtype):.3g}")
         torch.cuda.empty_cache()
-    print(f"\n[{cfg} {dtype_name}] {len(names)} calls per step, {len(uniq)} unique re-issued launch signatures")
+    print(f"\n[{cfg} {dtype_name}{' fused Adam' if fuse else ''}] {len(names)} calls per step, {len(uniq)} unique re-issued launch signatures")
     print(f"  {'entry point':28s} {'launches':>8s}  worst error per family (tolerance)")
     for name in sorted(table):
         r = table[name]
@@ -964,6 +1846,139 @@ def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name):
         print(f"  {name:28s} {r['launches']:8d}  {fams}")
     assert not failures, "\n".join(failures)
     assert table, f"{cfg}: no launch re-issued"
+
+
+def _direct_cases():
+    """(name, dtype, decoded args) of the entry points and forms that no benchmarked step issues: the partial-store forms
+    (P2P_FULL_PIXELS=0), generate() / hooked-step launches, the unbatched weight copies, the host-step Adam, an unaligned
+    dropout mask"""
+    def v(*a, **k):
+        return ("view", _vd(*a, **k))
+    P, BF, F = ("ptr", 0), L.BF16, L.F32
+    gs1 = ("gsrc", {"kind": 1, "nslabs": 0, "slab_stride": 0, "ld": 8, "coff": 0, "align": 0})
+    gs2 = ("gsrc", {"kind": 2, "nslabs": 2, "slab_stride": 3 * 16 * 16 * 4, "ld": 4, "coff": 0, "align": 0})
+    b1, b2, eps = float(np.float32(0.5)), float(np.float32(0.999)), float(np.float32(1e-7))
+    multi = ("views", tuple(tuple(sorted(d.items())) for d in (_vd(8, 8, 8, halo=1), _vd(8, 8, 40, halo=1, coff=32))))
+    return [
+        ("p2p_bce_logits", BF, [BF, 6, 3, 8, 8, v(8, 8, 1), 1 / 192, v(8, 8, 8, halo=1), v(8, 8, 8, halo=1), P, None]),
+        ("p2p_bce_logits_pad8", F, [F, 4, 4, 8, 8, v(8, 8, 1), 1 / 256, v(8, 8, 8, halo=1), None, P, None]),
+        ("p2p_tanh_l1_fwd", BF, [BF, 3, 16, 16, 3, v(16, 16, 3), v(16, 16, 8, halo=1), v(16, 16, 8, halo=1), 1 / 2304, P, P, None]),
+        ("p2p_tanh_l1_fwd", F, [F, 3, 16, 16, 4, v(16, 16, 4), v(16, 16, 8, halo=1), v(16, 16, 8, halo=1), 1 / 3072, P, None, None]),
+        ("p2p_tanh_l1_bwd", BF, [BF, 3, 16, 16, 3, v(16, 16, 8, halo=1), v(16, 16, 8, halo=1), gs1, gs2, 1e-3, v(16, 16, 4, halo=1),
+                                 None]),
+        ("p2p_tanh_l1_bwd", F, [F, 3, 16, 16, 4, v(16, 16, 8, halo=1), v(16, 16, 8, halo=1), gs1, None, 1e-3, v(16, 16, 4, halo=1),
+                                None]),
+        ("p2p_colsum", F, [P, 37, 19, 0.5, P, None]),
+        ("p2p_hist_normalize", F, [P, 3, P, None]),
+        ("p2p_pack_pair", BF, [BF, 2, 8, 8, P, P, v(8, 8, 8, halo=1), v(8, 8, 40, halo=1, coff=32), v(8, 8, 8, halo=1),
+                               v(8, 8, 8, halo=1), None]),
+        ("p2p_pack_pair_idx", F, [F, 2, 8, 8, P, P, v(8, 8, 8, halo=1), v(8, 8, 40, halo=1, coff=32), v(8, 8, 8, halo=1),
+                                  v(8, 8, 8, halo=1), None]),
+        ("p2p_pack_input", BF, [BF, 2, 8, 8, 3, P, 0, v(8, 8, 8, halo=1, coff=2, align=4), None]),
+        ("p2p_pack_input", F, [F, 2, 8, 8, 1, P, 1, v(8, 8, 4, halo=1), None]),
+        ("p2p_pack_input_multi", BF, [BF, 2, 8, 8, 4, P, 0, multi, 2, None]),
+        ("p2p_pack_input_multi", BF, [BF, 2, 8, 8, 1, P, 1, multi, 2, None]),
+        ("p2p_unpack", BF, [BF, 2, 8, 8, 5, v(8, 8, 8, halo=1, coff=1, align=2), P, None]),
+        ("p2p_weight_prep", BF, [BF, P, 40, 24, P, P, None]),
+        ("p2p_weight_prep", F, [F, P, 64, 64, P, None, None]),
+        ("p2p_weight_prep_pad", BF, [BF, P, 4, 64, P, 32, 64, P, 64, 8, None]),
+        ("p2p_adam_flat", F, [P, P, P, P, 10007, 1, ADAM_LR, b1, b2, eps, 1.0, None]),
+        ("p2p_dropout_mask", F, [P, 1003, 77, 5, None]),
+        ("p2p_dropout_mask_dev", F, [P, 1001, 77, P, 4, 64, None]),
+    ]
+
+
+DIRECT = _direct_cases()
+
+
+@pytest.mark.parametrize("k", range(len(DIRECT)), ids=[f"{n}-{'bf16' if d == L.BF16 else 'f32'}" for n, d, _ in DIRECT])
+def test_entry_points_no_benchmarked_step_issues(k):
+    name, dtype, dec = DIRECT[k]
+    errs = _reissue(name, dec, seed=2000 + k)
+    bad = {f: e for f, e in errs.items() if not e < _tol(f, dtype)}
+    print(f"\n  {name}: " + ", ".join(f"{f} {e:.2e}" for f, e in sorted(errs.items())))
+    assert not bad, f"{name}: {bad}"
+
+
+def test_every_checker_runs_somewhere():
+    """an entry point with a checker is either in a benchmarked step's recording (test above) or in DIRECT; this lists the ones
+    that only DIRECT reaches, so that a checker cannot silently go unused"""
+    direct = {n for n, _, _ in DIRECT}
+    recorded_only = {"p2p_bce_logits_pad8", "p2p_tanh_l1_fwd_pair", "p2p_tanh_l1_bwd_pad8", "p2p_loss_partials_sum",
+                     "p2p_finish_losses", "p2p_hellinger_fwd", "p2p_hellinger_finish", "p2p_view_colsum", "p2p_colsum_batched",
+                     "p2p_weight_prep_batched", "p2p_adam_tick", "p2p_adam_flat_dev", "p2p_adam_prep_batched", "p2p_counter_add"}
+    new = {n for n, f in CHECKERS.items() if f in (_bce, _tanh_fwd, _tanh_bwd, _partials_sum, _finish_losses, _hellinger_fwd,
+                                                   _hellinger_finish, _hist_normalize, _colsum, _view_colsum, _colsum_batched,
+                                                   _pack_pair, _pack_input, _unpack, _weight_prep, _weight_prep_batched, _adam_tick,
+                                                   _adam_flat, _adam_prep, _dropout, _counter_add)}
+    assert new <= direct | recorded_only, sorted(new - direct - recorded_only)
+
+
+# ---------------------------------------------------------------------------------------------------------------- one Adam step
+ADAM_CASES = [(c, d, False) for c, d in CONFIGS] + [("c2", "bf16", True)]
+
+
+def _copy_sets(eng):
+    """(label, operand copy, new master, Cg, Cd, rows, cols, transposed) of every weight copy the engine keeps"""
+    for (sid, name), lw in eng.W.items():
+        store = eng._store(sid)
+        master = store.view(store.params, name + ".kernel").reshape(-1)
+        for tag, buf, rows, cols, tr in (("wn", lw.wn, E.up32(lw.cg), lw.lo_pad, False), ("wt", lw.wt, E.up32(lw.cd), lw.hi_pad, True),
+                                         ("wd", lw.wd, lw.cg, lw.cd, False)):
+            if buf is not None:
+                yield f"{sid}.{name}.{tag}", buf, master, lw.cg, lw.cd, rows, cols, tr
+
+
+@pytest.mark.parametrize("cfg,dtype_name,fuse", ADAM_CASES, ids=[f"{c}-{d}" + ("-fused" if f else "") for c, d, f in ADAM_CASES])
+def test_one_keras_update_per_parameter_per_step(cfg, dtype_name, fuse):
+    """The replayed step of a bench config moves every element of both networks' params / m / v by exactly one Keras Adam step
+    driven by the gradients the step left in `grads` (a duplicated or missing update is about one Adam step away), refreshes
+    every operand copy from the new master, and advances t and the dropout counter by one."""
+    eng, step = _build(cfg, dtype_name)
+    try:
+        eng.fuse_adam = fuse
+        step()
+        step()                          # eager, recorded
+        torch.cuda.synchronize()
+        assert len(eng._replays) == 1, f"{cfg}: the step was not recorded"
+        stores = (("G", eng.G), ("D", eng.D))
+        snap = {sid: (st.params.clone(), st.m.clone(), st.v.clone(), st.t, int(st.t_dev[0])) for sid, st in stores}
+        ctr = int(eng.mask_counter_dev[0])
+        step()                          # replayed
+        torch.cuda.synchronize()
+        lr, b1, b2, eps = eng.lr, eng.beta1, eng.beta2, eng.adam_eps
+        missed, worst = [], {}
+        for sid, st in stores:
+            p0, m0, v0, t_host, t_dev = snap[sid]
+            assert st.t == t_host + 1 and int(st.t_dev[0]) == t_dev + 1, f"{sid}: t {t_host} -> {st.t}, t_dev {t_dev} -> {int(st.t_dev[0])}"
+            g = st.grads.double()
+            pr, mr, vr = SL.keras_adam(p0.double(), g, m0.double(), v0.double(), t_dev + 1, lr, b1, b2, eps)
+            ep = (st.params.double() - pr).abs() / (1e-6 * pr.abs() + 1e-7)
+            em = (st.m.double() - mr).abs() / (1e-6 * torch.maximum(mr.abs(), torch.maximum(m0.double().abs(), g.abs())) + 1e-30)
+            ev = (st.v.double() - vr).abs() / (5e-5 * vr.abs() + 1e-30)
+            for fam, e in (("p", ep), ("m", em), ("v", ev)):
+                worst[f"{sid} {fam}"] = float(e.max())
+            ok = (ep <= 1) & (em <= 1) & (ev <= 1)
+            covered = torch.zeros_like(ok)
+            for key, shape in st.shapes.items():
+                o, n = st.offsets[key], int(np.prod(shape))
+                covered[o:o + n] = True
+                if not bool(ok[o:o + n].all()):
+                    missed.append(f"{sid}.{key} ({int((~ok[o:o + n]).sum())} of {n})")
+            if not bool(ok[~covered].all()):
+                missed.append(f"{sid} alignment padding")
+        bad_copies = [label for label, buf, master, cg, cd, rows, cols, tr in _copy_sets(eng)
+                      if not torch.equal(_bits(buf), _bits(_copy_ref(master, cg, cd, rows, cols, tr, eng.tdt)))]
+        print(f"\n[{cfg} {dtype_name}{' fused Adam' if fuse else ''}] worst / bound: "
+              + ", ".join(f"{k} {e:.2e}" for k, e in sorted(worst.items())))
+        assert not missed, f"{cfg}: tensors not moved by exactly one Keras step: {missed}"
+        assert not bad_copies, f"{cfg}: operand copies that are not the rounding of the new master: {bad_copies}"
+        assert int(eng.mask_counter_dev[0]) == ctr + 1, f"dropout counter {ctr} -> {int(eng.mask_counter_dev[0])}"
+    finally:
+        del eng
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
 
 
 # ---------------------------------------------------------------------------------------------------------------- replay key
