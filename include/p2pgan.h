@@ -547,6 +547,27 @@ int p2p_gather_rows_i32(const int* table, int n_rows, int row_ints, const int* s
 int p2p_palette_relabel_batch(const int* src_idx, const int* tgt_idx, const int* palette, const int* perm, const int* inv,
                               int B, int n, int P, int C, int* src_out, int* tgt_out, int* pal_out, void* stream);
 
+/* ---- FID evaluation: InceptionV3 (Keras, include_top=False, pooling="avg", inference; reference frechet_inception_distance.py)
+ * All f32 in / f32 accumulate, fixed-order sums (bit-reproducible).  Views are NHWC p2p_tensor WITHOUT a halo: the convolution and
+ * the average pool predicate their taps on the image bounds.  Layer table and launch order: palette_and_histo_gan_amd/inception.py. */
+
+/* resize(image, (OH, OW, 3), order=0) of scikit-image 0.19 + preprocess_input ("tf" mode) of dense f32 images [N][H][W][C],
+ * C = 3 or 4: with `filter` (C = 4) the channel axis is smoothed by the 3-tap gaussian w1, w0, w1 (mode "mirror", in f64 as
+ * scipy evaluates it, stored f32); then out[n, o, p, q] = img[n, rows[o], cols[p], chans[q]] (device int32 index tables built on
+ * the host with scipy.ndimage.zoom), clipped to image n's [min, max], / 127.5, - 1.  minmax: device workspace of 2 N floats. */
+int p2p_inc_prep(int N, int H, int W, int C, const float* images, const int* rows, const int* cols, const int* chans, int OH,
+                 int OW, double w0, double w1, int filter, const p2p_tensor* out, float* minmax, void* stream);
+/* Conv2D (no bias, kernel kh x kw, stride, top/left zero padding) + BatchNorm(scale=False) + ReLU:
+ * out[n, oy, ox, co] = relu(scale[co] * sum_{ky,kx,ci} in[n, oy s - pad_top + ky, ox s - pad_left + kx, ci] w[(ky kw + kx) Cin + ci][co]
+ *                      + shift[co]),  scale = rsqrt(var + eps), shift = beta - mean scale (host, f64 -> f32).
+ * w: f32 [kh kw Cin][Cout], 16-byte aligned, Cout % 4 == 0.  `out` may be a channel slice of a wider buffer (any ld). */
+int p2p_inc_conv(int N, int H, int W, int Cin, int kh, int kw, int stride, int pad_top, int pad_left, int OH, int OW, int Cout,
+                 const p2p_tensor* in, const float* w, const float* scale, const float* shift, const p2p_tensor* out, void* stream);
+/* kind 0: max 3x3 / 2 "valid" (OH = (H - 3) / 2 + 1); kind 1: average 3x3 / 1 "same" over the taps inside the image (OH = H) */
+int p2p_inc_pool(int kind, int N, int H, int W, int C, const p2p_tensor* in, const p2p_tensor* out, void* stream);
+/* global average pool: out f32 [N][C] = mean over the H x W map */
+int p2p_inc_gap(int N, int H, int W, int C, const p2p_tensor* in, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,10 @@ SIGNATURES = {
     "p2p_sprites_rgba_batch": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "p2p_gather_rows_i32": [_vp, _i, _i, _vp, _i, _vp, _vp],
     "p2p_palette_relabel_batch": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "p2p_inc_prep": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _i, _TP, _vp, _vp],
+    "p2p_inc_conv": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _TP, _vp, _vp, _vp, _TP, _vp],
+    "p2p_inc_pool": [_i, _i, _i, _i, _i, _TP, _TP, _vp],
+    "p2p_inc_gap": [_i, _i, _i, _i, _TP, _vp, _vp],
 }
 SPECIAL = {"p2p_last_error": ([], C.c_char_p),
            "p2p_replay_fn_index": ([C.c_char_p], C.c_int), "p2p_replay_fn_nargs": ([_i], C.c_int),

@@ -67,6 +67,7 @@ constexpr Entry TABLE[] = {
     P2P_E(p2p_stream_wait_event) P2P_E(p2p_arm_stop_event) P2P_E(p2p_disarm_stop_event) P2P_E(p2p_png_unfilter) P2P_E(p2p_sprites_rgba_batch)
     P2P_E(p2p_gather_rows_i32) P2P_E(p2p_palette_relabel_batch) P2P_E(p2p_hist_normalize_bwd)
     P2P_E(p2p_rgbuv_hist_bwd) P2P_E(p2p_rgbuv_hist_general_bwd) P2P_E(p2p_softmax_bwd)
+    P2P_E(p2p_inc_prep) P2P_E(p2p_inc_conv) P2P_E(p2p_inc_pool) P2P_E(p2p_inc_gap)
 };
 #undef P2P_E
 constexpr int NFN = (int)(sizeof(TABLE) / sizeof(TABLE[0]));

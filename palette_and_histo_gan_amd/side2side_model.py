@@ -5,7 +5,8 @@ Kept: constructor signature, fit/do_fit call order (examples -> loop over train_
 attribute names subclasses use, report_l1 over TEST_SIZE images (side2side_model.py:162-176).  Replaced: the TensorFlow
 summary writer -> ScalarLog (JSON lines + a real TensorBoard event file, scalars kept on the device until flush());
 tf.train.Checkpoint / CheckpointManager -> flat-tensor files with the same object structure; the matplotlib previews
-and the FID callback (needs an InceptionV3 download, frechet_inception_distance.py:76) are reported as skipped.
+are PNG sheets.  report_fid / the "evaluate_fid" callback run the HIP InceptionV3 of frechet_inception_distance.py when
+P2P_FID_WEIGHTS names a weights file; without one the callback is reported as skipped.
 """
 from abc import ABC, abstractmethod
 import datetime
@@ -233,7 +234,13 @@ class S2SModel(ABC):
                     l1_train, l1_test = self.report_l1(step=(step + 1) // update_steps)
                     print(f" L1: {float(l1_train):.5f} / {float(l1_test):.5f} (train/test)")
                 if "evaluate_fid" in callbacks:
-                    print("FID needs the InceptionV3 ImageNet weights (network fetch): skipped")
+                    from . import frechet_inception_distance as fid
+                    if fid.configured_weights() is None:
+                        print("FID needs the InceptionV3 ImageNet weights (network fetch): skipped")
+                    else:
+                        print(f"Calculating Fréchet Inception Distance at {(step + 1) / 1000}k with {TEST_SIZE} examples...")
+                        train_fid, test_fid = self.report_fid(step=(step + 1) // update_steps)
+                        print(f"FID: {train_fid:.3f} / {test_fid:.3f} (train/test)")
                 print(f"Step: {(step + 1) / 1000}k")
             self.train_step(batch, step, update_steps)
             if main and ((step + 1) % (update_steps * 5) == 0 or (step - starting_step + 1) == steps):
@@ -366,6 +373,20 @@ class S2SModel(ABC):
         from . import keras_weights
         keras_weights.import_model(self, os.path.join(self._model_path("discriminator"), "weights.p2pw.npz"),
                                    with_optimizer=False, which=("discriminator",))
+
+    def report_fid(self, num_images=TEST_SIZE, step=None):
+        """side2side_model.py:144-160: FID of the generated against the real images of the first num_images samples of each set
+        (frechet_inception_distance.compare; weights from P2P_FID_WEIGHTS, FileNotFoundError without them)"""
+        from . import frechet_inception_distance as fid
+        fid.weights_path()          # fail before generating anything
+        train_real_images, train_fake_images = self.select_examples_for_evaluation(num_images, self.train_ds)
+        test_real_images, test_fake_images = self.select_examples_for_evaluation(num_images, self.test_ds)
+        train_value = fid.compare(train_real_images, train_fake_images)
+        test_value = fid.compare(test_real_images, test_fake_images)
+        if self.summary_writer is not None and step is not None:
+            self.summary_writer.scalar("fid/train", train_value, step)
+            self.summary_writer.scalar("fid/test", test_value, step)
+        return train_value, test_value
 
     def report_l1(self, num_images=TEST_SIZE, step=None):
         """side2side_model.py:162-176"""
