@@ -402,6 +402,10 @@ int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1, float beta
 int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_t_dev,
                       float beta1, float beta2, float eps, float gscale, void* stream);
 int p2p_counter_add(long long* counter_dev, long long inc, void* stream);
+/* f32 gradient sum of a GradientTape (tape.py): a network's weight gradients over several calls, the two terms of a generator
+ * call's d(source).  dst = src when `first` is set (the first contribution), dst += src otherwise; n floats, 16-byte aligned,
+ * no atomics (bit-reproducible). */
+int p2p_grad_accumulate(float* dst, const float* src, long long n, int first, void* stream);
 
 /* master f32 W[16][Cg][Cd] -> wn (dtype, same layout; may be null) and wt (dtype, [16][Cd][Cg]; may be null). */
 int p2p_weight_prep(int dtype, const float* w, int Cg, int Cd, void* wn, void* wt, void* stream);

@@ -58,6 +58,7 @@ SIGNATURES = {
     "p2p_adam_tick": [_vp, _vp, _f, _f, _f, _vp],
     "p2p_adam_flat_dev": [_vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _vp],
     "p2p_counter_add": [_vp, _ll, _vp],
+    "p2p_grad_accumulate": [_vp, _vp, _ll, _i, _vp],
     "p2p_dropout_mask_dev": [_vp, _ll, _ll, _vp, _ll, _ll, _vp],
     "p2p_weight_prep": [_i, _vp, _i, _i, _vp, _vp, _vp],
     "p2p_weight_prep_batched": [_i, _vp, _i, _ll, _vp],

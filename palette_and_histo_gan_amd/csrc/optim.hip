@@ -92,6 +92,35 @@ extern "C" int p2p_counter_add(long long* counter_dev, long long inc, void* stre
     return p2p_check_launch("p2p_counter_add");
 }
 
+// f32 gradient sum of a GradientTape (tape.py): a network's weight gradients over several calls, the two terms of a generator
+// call's d(source).  dst = src for the first contribution, dst += src for every further one.  One thread per 16-byte chunk, no atomics: each element is one add in call
+// order, so the sum is bit-reproducible.
+__global__ void grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n, int first) {
+    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    long long stride = (long long)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        f32x4 s = *(const f32x4*)(src + i);
+        if (!first) {
+            f32x4 d = *(const f32x4*)(dst + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] = d[k] + s[k];
+        }
+        *(f32x4*)(dst + i) = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = n / 4 * 4; j < n; ++j) dst[j] = first ? src[j] : dst[j] + src[j];
+}
+
+extern "C" int p2p_grad_accumulate(float* dst, const float* src, long long n, int first, void* stream) {
+    P2P_REQUIRE(dst && src && n > 0, "p2p_grad_accumulate: bad args");
+    P2P_REQUIRE(((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0, "p2p_grad_accumulate: buffers must be 16-byte aligned");
+    long long blocks = (n / 4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    grad_accumulate_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(dst, src, n, first);
+    return p2p_check_launch("p2p_grad_accumulate");
+}
+
 // wn[t][g][d] = T(w[t][g][d]) for g < wn_rows, d < wn_cols;  wt[t][d][g] = T(w[t][g][d]) for d < wt_rows,
 // g < wt_cols; entries outside the real [Cg][Cd] block are written as zeros (channel padding of the edge
 // layers).  32x32 LDS tile transpose per tap.

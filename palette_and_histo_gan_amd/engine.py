@@ -383,6 +383,18 @@ class ParamStore:
     def g(self, name):
         return _p(self.grads, self.offsets[name])
 
+    def variable_name(self, t):
+        """name of the variable whose view `t` is (an entry of trainable_variables), or None"""
+        if not isinstance(t, torch.Tensor) or t.device != self.params.device or t.dtype != torch.float32:
+            return None
+        off = t.data_ptr() - self.params.data_ptr()
+        if off < 0 or off % 4 or off >= 4 * self.numel:
+            return None
+        if getattr(self, "_by_offset", None) is None:
+            self._by_offset = {o: k for k, o in self.offsets.items()}
+        name = self._by_offset.get(off // 4)
+        return name if name is not None and tuple(t.shape) == tuple(self.shapes[name]) else None
+
     def load(self, values):
         for k in self.shapes:
             self.view(self.params, k).copy_(torch.as_tensor(np.asarray(values[k]), dtype=torch.float32))
@@ -504,6 +516,12 @@ class Pix2PixEngine:
         self.splitk_target = int(os.environ.get("P2P_SPLITK_TARGET", "0"))
         self._prep_table = {}
         self._head_prepped = False
+        # tape calls (tape.py): arenas of activations per call, pooled by (network, images) once a tape is released; the
+        # workspaces they share per image count; the op-P copy of G.down1, prepared only when a tape needs d(source)
+        self._arena_pool, self._tape_ws = {}, {}
+        self._copies_version = 0
+        self._down1_wn, self._down1_wn_key = None, None
+        self.tape_refusal = None        # set by a model whose configuration has no tape path (data parallelism)
         # partial-pixel stores (the source channels of the last concat buffer, the halves of the discriminator's fake pixel) are
         # issued by the kernel that writes the rest of the pixel (0: separate stores in p2p_pack_pair, the r02 form)
         self.full_pixels = os.environ.get("P2P_FULL_PIXELS", "1") != "0"
@@ -585,14 +603,15 @@ class Pix2PixEngine:
     def _prep_tasks(self, part="all"):
         """Device table of p2p_prep_task descriptors (one per weight copy set); the pointers are stable for the life
         of the engine, so it is built once.  part = "head": the generator layers whose parameters lie in front of the last
-        gradient bucket (what _adam_head updates early), "rest": the others, "all": every layer."""
+        gradient bucket (what _adam_head updates early), "rest": the others, "all": every layer, "G" / "D": one network's
+        layers (the per-network optimizer step, apply_adam_store)."""
         if self._prep_table.get(part) is not None:
             return self._prep_table[part]
         head_end = self.G.buckets[-1][0] if len(self.G.buckets) >= 2 else 0
         specs = []
         for (sid, name), lw in self.W.items():
             in_head = sid == "G" and self.G.offsets[name + ".kernel"] + 16 * lw.cg * lw.cd <= head_end
-            if (part == "head" and not in_head) or (part == "rest" and in_head):
+            if (part == "head" and not in_head) or (part == "rest" and in_head) or (part in ("G", "D") and sid != part):
                 continue
             master = self._store(sid).p(name + ".kernel")
             if lw.wt is not None or lw.wn is not None:
@@ -677,6 +696,7 @@ class Pix2PixEngine:
 
     def refresh_weight_copies(self, part="all"):
         """Re-derives the per-layer weight copies from the f32 masters; runs after every Adam step (one launch per part)."""
+        self._copies_version += 1
         raw, ntasks, total = self._prep_tasks(part)
         if ntasks:
             L.call("p2p_weight_prep_batched", self.dtype, _p(raw), ntasks, total, _stream())
@@ -700,8 +720,16 @@ class Pix2PixEngine:
     def plan(self, B):
         if B in self.plans:
             return self.plans[B]
-        S, dt, dev, tdt = self.S, self.dtype, self.device, self.tdt
         P = {"B": B}
+        self._alloc_generator(P, B)
+        self._alloc_discriminator(P, 2 * B, B)
+        self._alloc_workspaces(P, B)
+        self.plans[B] = P
+        return P
+
+    def _alloc_generator(self, P, B):
+        """the generator's activations, gradient sources and norm partials for B images"""
+        S, dt, dev, tdt = self.S, self.dtype, self.device, self.tdt
         # concat buffers c1..c6: [up_k output | skip]   (networks.py:92-94); c6 = [up6 | source | zero pad]
         skips = list(reversed(DOWN_FILTERS[:-1])) + [self.in_ch]
         P["c"] = [None]
@@ -750,29 +778,38 @@ class Pix2PixEngine:
         # generator head
         P["z"] = DenseBuf(B, S, S, self.out_ch, tdt, dev)
         P["dz"] = HaloBuf(B, S, S, self.dz_ch, dt, dev)
-        # discriminator: images [0,B) = [real | source], [B,2B) = [fake | source]   (networks.py:45)
+
+    def _alloc_discriminator(self, P, N, B=None):
+        """the discriminator's buffers for N images.  B given: the train step's layout, N = 2B -- images [0,B) = [real | source],
+        [B,2B) = [fake | source] (networks.py:45) -- plus the generator path's own buffers of B images; B=None: one standalone
+        call on N images (a tape call, tape.py)"""
+        S, dt, dev, tdt = self.S, self.dtype, self.device, self.tdt
         h2 = S // 2
-        P["dcat"] = HaloBuf(2 * B, S, S, self.dcat_ch, dt, dev)
-        P["d_act"] = HaloBuf(2 * B, h2, h2, 64, dt, dev)
-        P["logits"] = DenseBuf(2 * B, h2, h2, 1, tdt, dev)
-        P["dld"] = HaloBuf(2 * B, h2, h2, 8, dt, dev)
-        P["dlg"] = HaloBuf(B, h2, h2, 8, dt, dev)
-        P["g_dact"] = DenseBuf(2 * B, h2, h2, 64, tdt, dev)
-        P["d_draw"] = HaloBuf(2 * B, h2, h2, 64, dt, dev)
-        P["d_draw_g"] = HaloBuf(B, h2, h2, 64, dt, dev)      # generator path: own buffer (D.down's wgrad may still read d_draw)
-        P["g_dact_g"] = DenseBuf(B, h2, h2, 64, tdt, dev)
+        P["dcat"] = HaloBuf(N, S, S, self.dcat_ch, dt, dev)
+        P["d_act"] = HaloBuf(N, h2, h2, 64, dt, dev)
+        P["logits"] = DenseBuf(N, h2, h2, 1, tdt, dev)
+        P["dld"] = HaloBuf(N, h2, h2, 8, dt, dev)
+        if B is not None:
+            P["dlg"] = HaloBuf(B, h2, h2, 8, dt, dev)
+        P["g_dact"] = DenseBuf(N, h2, h2, 64, tdt, dev)
+        P["d_draw"] = HaloBuf(N, h2, h2, 64, dt, dev)
+        if B is not None:
+            P["d_draw_g"] = HaloBuf(B, h2, h2, 64, dt, dev)      # generator path: own buffer (D.down's wgrad may still read d_draw)
+            P["g_dact_g"] = DenseBuf(B, h2, h2, 64, tdt, dev)
         # d(D.first)/d(fake): only the image's channels carry a gradient; with 4 of them the buffer is dense 4-channel pixels, so the
         # kernel that writes them stores whole pixels (in an 8-channel pixel the 8 of 16 bytes are a partial sector write)
-        P["g_dcat"] = DenseBuf(B, S, S, 4 if (self.in_ch == 4 and self.full_pixels) else self.dcat_ch, tdt, dev)
+        P["g_dcat"] = DenseBuf(N if B is None else B, S, S, 4 if (self.in_ch == 4 and self.full_pixels) else self.dcat_ch, tdt, dev)
         if not self.use_mfma:
-            P["d_raw"] = DenseBuf(2 * B, h2, h2, 64, tdt, dev)
+            P["d_raw"] = DenseBuf(N, h2, h2, 64, tdt, dev)
+
+    def _alloc_workspaces(self, P, B):
+        """norm, conv-epilogue, split-K and weight-gradient workspaces (their contents live for one launch or one layer)"""
+        dev = self.device
         P["nws"] = torch.empty(max(B, 2) * 16 * 1024 * 2, dtype=torch.float32, device=dev)   # norm split partials [N][16][C<=1024][2]
         P["spart"] = torch.empty(4 * 1024 * 1024, dtype=torch.float32, device=dev)    # conv-epilogue statistics [N][slots][C][2]
         # split-K / wgrad workspaces
         P["slabs"] = torch.empty(self._max_slab_elems(B), dtype=torch.float32, device=dev)
         P["wws"] = torch.empty(self._max_wgrad_ws(B) // 4 + 4, dtype=torch.float32, device=dev)
-        self.plans[B] = P
-        return P
 
     # -- heuristics for the MFMA kernels --------------------------------------------------------------
     def _splitk(self, op, B, lh, cg, cd):
@@ -845,12 +882,12 @@ class Pix2PixEngine:
 
     # ------------------------------------------------------------------ kernel wrappers
     def _conv(self, P, op, sid, name, N, lh, in_view, out_view, stride=2, ncols=None, bias=None, act=L.ACT_NONE,
-              tmp=None, want_stats=False, slab_key=None):
+              tmp=None, want_stats=False, slab_key=None, w_p=None):
         """op G (gathers the hi view, writes lo) or op P (gathers the lo view, writes hi).  Returns (raw_kind,
         nslabs): the result is in the output view in the activation dtype (1, 1) or in f32 split-K slabs (2, nslabs):
         the shared workspace P['slabs'], or -- with `slab_key` -- a buffer of its own that stays valid until the same
         layer runs again, returned as a third element (2, nslabs, tensor).  `ncols` limits op P to the first ncols
-        output channels."""
+        output channels; `w_p`: op-P operand copy of a layer that has none in self.W (G.down1, _down1_wn)."""
         lw = self.W[(sid, name)]
         cg, cd = lw.cg, lw.cd
         hi, lo = (in_view, out_view) if op == L.OP_G else (out_view, in_view)
@@ -886,7 +923,7 @@ class Pix2PixEngine:
             if op == L.OP_G:
                 cin_pad, nc, rows, w = lw.hi_pad, cd, up32(cd), _p(lw.wt)
             else:
-                cin_pad, nc, rows, w = lw.lo_pad, (ncols or cg), up32(cg), self._wn(sid, name)
+                cin_pad, nc, rows, w = lw.lo_pad, (ncols or cg), up32(cg), w_p or self._wn(sid, name)
             if self.use_conv_fewout and L.lib().p2p_conv_fewout_ok(op, stride, self.dtype, N, lh, lh, cin_pad, nc):
                 entry = "p2p_conv_fewout"
             elif self.use_conv_fewin and L.lib().p2p_conv_fewin_ok(op, stride, self.dtype, N, lh, lh, cin_pad, nc):
@@ -1912,3 +1949,186 @@ class Pix2PixEngine:
         out = torch.empty((B, S, S, self.out_ch), dtype=torch.float32, device=self.device)
         L.call("p2p_unpack", self.dtype, B, S, S, self.out_ch, C.byref(fake_view), _p(out), _stream())
         return out
+
+    # ------------------------------------------------------------------ tape calls (tape.py: tf_compat.tf.GradientTape)
+    # A custom train_step (pix2pix_model.py:62-89 is the reference's) calls the networks under a GradientTape.  Every call runs on
+    # an ARENA of its own (the plan's generator or discriminator part for its image count, plus the workspaces shared by the tape
+    # calls of that count), so one tape may call G twice and D three times; the VJP of a call runs the same backward kernels as
+    # the fused step on that arena.  The fused and replayed steps keep their plans and never see an arena.
+    def tape_arena(self, kind, N):
+        """an arena for one tape call of network `kind` ("G" / "D") on N images: pooled, or allocated"""
+        pool = self._arena_pool.setdefault((kind, N), [])
+        if pool:
+            return pool.pop()
+        P = {"B": N, "kind": kind}
+        if kind == "G":
+            self._alloc_generator(P, N)
+            P["fake"] = DenseBuf(N, self.S, self.S, self.out_ch, self.tdt, self.device)     # tanh(z) in the activation dtype
+        else:
+            self._alloc_discriminator(P, N)
+        ws = self._tape_ws.get(N)
+        if ws is None:
+            ws = {}
+            self._alloc_workspaces(ws, N)
+            self._tape_ws[N] = ws
+        P.update(ws)
+        return P
+
+    def release_tape_arena(self, P):
+        self._arena_pool[(P["kind"], P["B"])].append(P)
+
+    def free_tape_arenas(self):
+        """drops the pooled arenas and their workspaces (the memory returns to torch's allocator)"""
+        self._arena_pool.clear()
+        self._tape_ws.clear()
+
+    @staticmethod
+    def arena_bytes(P):
+        """device bytes an arena holds besides the shared workspaces"""
+        seen, total = set(), 0
+
+        def add(t):
+            nonlocal total
+            if isinstance(t, (HaloBuf, DenseBuf)):
+                t = t._flat if isinstance(t, HaloBuf) else t.t
+            if isinstance(t, torch.Tensor) and t.data_ptr() not in seen:
+                seen.add(t.data_ptr())
+                total += t.numel() * t.element_size()
+            elif isinstance(t, (list, tuple)):
+                for x in t:
+                    add(x)
+            elif isinstance(t, dict):
+                for x in t.values():
+                    add(x)
+        add({k: v for k, v in P.items() if k not in ("nws", "spart", "slabs", "wws")})
+        return total
+
+    def tape_generator_forward(self, P, source, masks=None):
+        """generator(source, training=True) on arena P: the f32 (B,S,S,out) image.  Dropout: the masks are drawn at the device
+        counter (offset 0), which then advances by one -- one tape step of the reference's form draws the fused step's masks."""
+        B, S = P["B"], self.S
+        src_t = self._to_device(source, self.in_ch, B)
+        self._dp, self._batch_offset = None, 0
+        self._pack_source(P, src_t)
+        P["early_masks"] = False
+        self.generator_forward(P, masks)
+        L.call("p2p_counter_add", _p(self.mask_counter_dev), 1, _stream())
+        out = torch.empty((B, S, S, self.out_ch), dtype=torch.float32, device=self.device)
+        fake = P["fake"].view()
+        L.call("p2p_tanh_l1_fwd", self.dtype, B, S, S, self.out_ch, C.byref(P["z"].view()), C.byref(fake), C.byref(fake), 0.0,
+               _p(self.loss_part, 4 * 256), _p(out), _stream())
+        return out
+
+    def _gradient_f32(self, g, shape):
+        """an upstream gradient as a dense, 16-byte aligned f32 device tensor"""
+        g = g.detach().to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+        return g if g.data_ptr() % 16 == 0 else g.clone()
+
+    def _down1_copy(self):
+        """G.down1's op-P operand copy (the fused step never needs it: no gradient flows into the source image), prepared when a
+        tape asks for d(source) and re-derived once the generator's weights have changed"""
+        key = (self.G.t, self._copies_version)
+        lw = self.W[("G", "down1")]
+        if self._down1_wn is None:
+            self._down1_wn = torch.zeros(16 * up32(lw.cg) * lw.lo_pad, dtype=self.tdt, device=self.device)
+        if self._down1_wn_key != key:
+            L.call("p2p_weight_prep_pad", self.dtype, self.G.p("down1.kernel"), lw.cg, lw.cd, _p(self._down1_wn), up32(lw.cg),
+                   lw.lo_pad, None, 0, 0, _stream())
+            self._down1_wn_key = key
+        return _p(self._down1_wn)
+
+    def tape_generator_backward(self, P, d_image, need_source_grad):
+        """VJP of one generator call from d(image) (f32): the weight gradients into G.grads (complete once the side stream is
+        joined) and, if asked, d(source) as a dense f32 (B,S,S,in) tensor.  The source feeds down1 and the last skip connection
+        (concat 6 = [up6 | source], networks.py:92-94), so d(source) is G.down1 transposed into the image channels (the shape of
+        D.down's data gradient) plus the source channels of the head's data gradient."""
+        B, S, ic = P["B"], self.S, self.in_ch
+        g = self._gradient_f32(d_image, (B, S, S, self.out_ch))
+        gx = L.GSrc(g.data_ptr(), 2, 1, B * S * S * self.out_ch, self.out_ch, 0)
+        fake = P["fake"].view()
+        if self.full_pixels and self.out_ch == 4 and self.dz_ch == 8:
+            L.call("p2p_tanh_l1_bwd_pad8", self.dtype, B, S, S, C.byref(fake), C.byref(fake), None, C.byref(gx), 0.0,
+                   C.byref(P["dz"].view()), _stream())
+        else:
+            L.call("p2p_tanh_l1_bwd", self.dtype, B, S, S, self.out_ch, C.byref(fake), C.byref(fake), None, C.byref(gx), 0.0,
+                   C.byref(P["dz"].view()), _stream())
+        P["head_dbias_done"] = False
+        self.generator_backward(P)
+        d_src = None
+        if need_source_grad:
+            buf = P.get("g_src")
+            if buf is None:
+                buf = P["g_src"] = DenseBuf(B, S, S, 4 if (ic == 4 and self.full_pixels) else self.src_ch, self.tdt, self.device)
+            self._conv(P, L.OP_P, "G", "down1", B, S // 2, P["dd"][1].view(), buf.view(), ncols=ic,
+                       w_p=self._down1_copy() if self.use_mfma else None)
+            skip = P.get("g_c6")
+            if skip is None:
+                skip = P["g_c6"] = DenseBuf(B, S, S, self.c6_ch, self.tdt, self.device)
+            self._conv(P, L.OP_P, "G", "last", B, S, P["dz"].view(), skip.view(), stride=1, ncols=UP_FILTERS[5] + ic)
+            d_src = torch.empty((B, S, S, ic), dtype=torch.float32, device=self.device)
+            d_skip = torch.empty((B, S, S, ic), dtype=torch.float32, device=self.device)
+            L.call("p2p_unpack", self.dtype, B, S, S, ic, C.byref(buf.view()), _p(d_src), _stream())
+            L.call("p2p_unpack", self.dtype, B, S, S, ic, C.byref(skip.view(coff=UP_FILTERS[5])), _p(d_skip), _stream())
+            L.call("p2p_grad_accumulate", _p(d_src), _p(d_skip), d_src.numel(), 0, _stream())
+        self.side.join()
+        self._adam_head_ev = None
+        P["keep"] = g
+        return d_src
+
+    def tape_discriminator_forward(self, P, first, second):
+        """discriminator([first, second], training=True) on arena P: f32 logits (N,S/2,S/2,1)"""
+        N, S, ic, h2 = P["B"], self.S, self.in_ch, self.S // 2
+        self._pack(P, self._to_device(first, ic, N), P["dcat"].view(coff=0), ic)
+        self._pack(P, self._to_device(second, ic, N), P["dcat"].view(coff=ic), ic)
+        self.discriminator_forward(P, N)
+        out = torch.empty((N, h2, h2, 1), dtype=torch.float32, device=self.device)
+        L.call("p2p_unpack", self.dtype, N, h2, h2, 1, C.byref(P["logits"].view()), _p(out), _stream())
+        return out
+
+    def tape_discriminator_backward(self, P, d_logits, weights, need_first, need_second):
+        """VJP of one standalone discriminator call (discriminator_backward for one input pair): with `weights`, the weight
+        gradients into D.grads; d(first input) / d(second input) as dense f32 (N,S,S,in) tensors where asked (else None),
+        through D.down's data gradient into the image channels."""
+        N, S, ic, h2 = P["B"], self.S, self.in_ch, self.S // 2
+        g = self._gradient_f32(d_logits, (N, h2, h2, 1))
+        L.call("p2p_pack_input", self.dtype, N, h2, h2, 1, _p(g), 0, C.byref(P["dld"].view()), _stream())     # channel 0 of 8
+        dld, d_act, d_draw = P["dld"].view(), P["d_act"].view(), P["d_draw"].view()
+        if weights:
+            self._wgrad(P, "D", "last", N, h2, d_act, dld, stride=1, dbias=self.D.g("last.bias"))
+        if not self._d_last_dgrad_gated(N, h2, dld, d_act, d_draw):
+            self._conv(P, L.OP_P, "D", "last", N, h2, dld, P["g_dact"].view(), stride=1)
+            self._act_bwd(N, h2, 64, d_act, P["g_dact"].gsrc(), None, d_draw, fork_follows=weights)
+        if weights:
+            self._wgrad(P, "D", "down", N, h2, P["dcat"].view(), d_draw)
+        outs = [None, None]
+        if need_first or need_second:
+            nc = 2 * ic if need_second else ic
+            buf = P["g_dcat"]
+            if buf.c < nc:
+                buf = P.get("g_dcat2")
+                if buf is None:
+                    buf = P["g_dcat2"] = DenseBuf(N, S, S, self.dcat_ch, self.tdt, self.device)
+            self._conv(P, L.OP_P, "D", "down", N, h2, d_draw, buf.view(), ncols=nc)
+            for k, want in enumerate((need_first, need_second)):
+                if want:
+                    outs[k] = torch.empty((N, S, S, ic), dtype=torch.float32, device=self.device)
+                    L.call("p2p_unpack", self.dtype, N, S, S, ic, C.byref(buf.view(coff=k * ic)), _p(outs[k]), _stream())
+        self.side.join()
+        P["keep"] = g
+        return outs
+
+    def tape_collect(self, sid, dst, first):
+        """the weight gradients of the backward just joined (the store's scratch `grads`) into a tape's f32 buffer: dst = grads on
+        the network's first contribution, dst += grads after it"""
+        store = self._store(sid)
+        L.call("p2p_grad_accumulate", _p(dst), _p(store.grads), store.numel, int(bool(first)), _stream())
+
+    def apply_adam_store(self, store, grads):
+        """One optimizer's step (Adam.apply_gradients of a custom train_step): the store's own t / t_dev / lr_t_dev, Keras Adam on
+        its flat buffer from `grads` (f32, the store's layout), then its layers' weight copies.  apply_adam is the fused step's
+        form for both networks; the dropout counter is not advanced here (a tape's generator calls advance it)."""
+        store.t += 1
+        L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
+        L.call("p2p_adam_flat_dev", _p(store.params), _p(grads), _p(store.m), _p(store.v), store.numel, _p(store.lr_t_dev),
+               self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+        self.refresh_weight_copies("G" if store is self.G else "D")

@@ -10,10 +10,13 @@ A bound handle has the call surface the reference uses: `generator(source, train
 `discriminator([target, source], training=True)`, `.name`, `.trainable_variables` / `.trainable_weights`,
 `.count_params()`, `.get_weights()` / `.set_weights()` (Keras variable order, Keras layouts: HWIO for Conv2D,
 (kh, kw, Cout, Cin) for Conv2DTranspose).
+While a tf_compat.tf.GradientTape records, a call returns a differentiable f32 tensor (tape.py); otherwise a detached one.
 """
 from collections import OrderedDict
 
 import numpy as np
+
+from . import tape as _tape
 
 
 class _Handle:
@@ -69,12 +72,16 @@ class UnetGeneratorHandle(_Handle):
             raise ValueError("last_activation must be 'tanh' or 'softmax' (the two heads the reference uses)")
         self.input_channels, self.output_channels, self.last_activation = input_channels, output_channels, last_activation
 
-    def __call__(self, source_image, training=True):
-        # the reference passes training=True everywhere (pix2pix_model.py:60,67): dropout is always on
+    def __call__(self, source_image, training=True, masks=None):
+        # the reference passes training=True everywhere (pix2pix_model.py:60,67): dropout is always on.  masks: the six dropout
+        # keep-masks (as the engine's entry points take them) instead of the device's draw
         eng = self._bound()
+        tape = _tape.recording()
+        if tape is not None:
+            return tape.call_generator(eng, source_image, masks)
         if eng.head == "softmax":
-            return eng.generate_indexed(source_image, with_probs=True)[1]
-        return eng.generate(source_image)
+            return eng.generate_indexed(source_image, masks=masks, with_probs=True)[1]
+        return eng.generate(source_image, masks=masks)
 
 
 class PatchDiscriminatorHandle(_Handle):
@@ -84,7 +91,11 @@ class PatchDiscriminatorHandle(_Handle):
 
     def __call__(self, inputs, training=True):
         target_image, source_image = inputs
-        return self._bound().discriminate(target_image, source_image)
+        eng = self._bound()
+        tape = _tape.recording()
+        if tape is not None:
+            return tape.call_discriminator(eng, target_image, source_image)
+        return eng.discriminate(target_image, source_image)
 
 
 def UnetGenerator(input_channels, output_channels, last_activation):

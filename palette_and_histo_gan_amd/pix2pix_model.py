@@ -82,11 +82,45 @@ class Adam:
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
-        self._store = None
+        self._store = self._engine = None
 
     @property
     def iterations(self):
         return 0 if self._store is None else self._store.t
+
+    def apply_gradients(self, grads_and_vars):
+        """One Adam step of this optimizer's network (a custom train_step, tf_compat.tf.GradientTape): `grads_and_vars` pairs a
+        gradient with every one of the network's trainable_variables.  The gradients a tape returned are views of its flat
+        buffer, which Adam reads in place; other tensors are copied into a flat buffer first.  Advances `iterations` of this
+        optimizer only (engine.apply_adam_store)."""
+        store, eng = self._store, self._engine
+        if store is None:
+            raise RuntimeError("this optimizer is not bound to a network yet (a Pix2Pix*Model binds it in its constructor)")
+        grads = {}
+        for g, v in grads_and_vars:
+            name = store.variable_name(v)
+            if name is None:
+                raise ValueError(f"apply_gradients: a variable of shape {tuple(getattr(v, 'shape', ()))} is not one of the "
+                                 f"network this optimizer updates")
+            if g is None:
+                raise ValueError(f"apply_gradients: no gradient for {name} (the loss does not depend on this network)")
+            if tuple(g.shape) != tuple(store.shapes[name]):
+                raise ValueError(f"apply_gradients: gradient of shape {tuple(g.shape)} for {name} {tuple(store.shapes[name])}")
+            grads[name] = g
+        missing = [k for k in store.shapes if k not in grads]
+        if missing:
+            raise ValueError(f"apply_gradients steps the whole network: no gradient for {', '.join(missing)}")
+        base = next(iter(grads.values()))._base
+        if base is not None and base.dtype == torch.float32 and base.device == store.params.device and base.numel() == store.numel \
+                and base.is_contiguous() \
+                and all(g._base is base and g.is_contiguous() and g.data_ptr() == base.data_ptr() + 4 * store.offsets[k]
+                        for k, g in grads.items()):
+            flat = base             # the tape's own buffer
+        else:
+            flat = torch.zeros(store.numel, dtype=torch.float32, device=store.params.device)
+            for k, g in grads.items():
+                store.view(flat, k).copy_(g)
+        eng.apply_adam_store(store, flat)
 
 
 class Pix2PixModel(S2SModel):
@@ -141,6 +175,10 @@ class Pix2PixModel(S2SModel):
         g.bind(eng, eng.G)
         d.bind(eng, eng.D)
         go._store, do._store = eng.G, eng.D
+        go._engine = do._engine = eng
+        if self.data_parallel is not None:
+            eng.tape_refusal = ("a GradientTape step runs on one GPU (as the hooked steps): this model trains data-parallel, "
+                                "its fused train_step issues the collectives")
         return eng
 
     # -- losses as standalone evaluations (pix2pix_model.py:44-56); train_step computes them fused ----------------

@@ -53,6 +53,8 @@ class ScalarLog:
         self._rows = []          # (name, value or device tensor, step, wall time)
 
     def scalar(self, name, value, step):
+        if isinstance(value, torch.Tensor):
+            value = value.detach()          # a custom train_step's losses carry a tape's graph: the log keeps the value only
         self._rows.append((name, value, int(step), time.time()))
         if len(self._rows) >= self.max_pending:
             self.flush()

@@ -7,8 +7,11 @@ imports changed (examples/experiments.py runs the same workflow
 `tf.random.set_seed(s)` sets the default seed of everything created afterwards that takes `seed=None`: the dataset shuffles
 and augmentation draws (dataset_utils.load_rgba_ds / load_indexed_ds) and the models' weight initialisation and dropout
 streams (pix2pix_model.Pix2Pix*Model).  The random streams are numpy's and the device's, not TensorFlow's.
+
+`tf.GradientTape(persistent=False)` records the HIP networks' calls for a custom train_step (tape.py).
 """
 from .configuration import SEED
+from .tape import GradientTape
 
 _state = {"seed": SEED}
 
@@ -38,6 +41,7 @@ class _Test:
 class _TF:
     random = _Random()
     test = _Test()
+    GradientTape = GradientTape
 
     @property
     def __version__(self):
