@@ -1,4 +1,5 @@
-"""The float64 references of tests/test_step_launches_gpu.py (tests/step_launches.py) against the oracle's convolutions."""
+"""The float64 references of tests/test_step_launches_gpu.py (tests/step_launches.py) against the oracle's convolutions, and the
+host-only census of the kernel variants a train step takes at every batch against the batches the GPU tests run."""
 import numpy as np
 import pytest
 import torch
@@ -100,3 +101,75 @@ def test_bf16_round_matches_torch_at_ties():
     rng = np.random.default_rng(8)
     x = (rng.normal(size=4096) * 10.0 ** rng.integers(-6, 6, size=4096)).astype(np.float32)
     assert np.array_equal(SL.bf16_round(x).view(np.uint32), torch.as_tensor(x).to(torch.bfloat16).float().numpy().view(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------------------- census
+CASES = sorted(SL.CASE_RULES)
+_COVERAGE = {}
+
+
+def _coverage(case, batches=None):
+    """the census of a case over B = 1 .. 512, computed once per (case, batch list)"""
+    batches = SL.OFF_BENCH_BATCHES[case] if batches is None else tuple(batches)
+    if (case, batches) not in _COVERAGE:
+        _COVERAGE[(case, batches)] = SL.coverage(case, batches)
+    return _COVERAGE[(case, batches)]
+
+
+def _problems(case, batches):
+    """what keeps a batch list from satisfying the coverage condition of a case (empty: satisfied)"""
+    rule = SL.CASE_RULES[case]
+    below, missing, above, first = _coverage(case, batches)
+    out = []
+    if not set(rule["required"]) <= set(batches):
+        out.append(f"required batches missing: {sorted(set(rule['required']) - set(batches))}")
+    if max(batches) > rule["cap"]:
+        out.append(f"batch {max(batches)} is above the cap {rule['cap']}")
+    if missing:
+        out.append(f"{len(missing)} variant classes no tested batch produces, e.g. first at B={first[missing[0]]}: "
+                   f"{SL.describe_key(missing[0])}")
+    if len(above) > rule["above_cap_max"]:
+        out.append(f"{len(above)} classes first appear above the cap, {rule['above_cap_max']} when the list was written")
+    return out
+
+
+@pytest.mark.parametrize("case", CASES, ids=["-".join(map(str, c)) for c in CASES])
+def test_off_benchmark_batches_reach_every_variant_class_below_the_cap(case):
+    """Every variant class (step_launches.variant_key) that the engine's own dry run produces for any batch from 1 to the cap is
+    produced by a batch of OFF_BENCH_CASES or by the case's bench config, the required batches are in the list, and the classes
+    that first appear above the cap are listed and their number is bounded."""
+    rule, batches = SL.CASE_RULES[case], SL.OFF_BENCH_BATCHES[case]
+    below, missing, above, first = _coverage(case, batches)
+    print(f"\n[{' '.join(map(str, case))}] {len(below)} variant classes up to batch {rule['cap']}, covered by:")
+    for k in sorted(below, key=lambda k: (below[k] or 0, repr(k))):
+        print(f"  B={below[k]!s:>4s}  {SL.describe_key(k)}")
+    print(f"  {len(above)} classes first appear above the cap (upper side covered by the bench batches {rule['bench']}):")
+    for k in sorted(above, key=lambda k: (above[k], repr(k))):
+        print(f"  first at B={above[k]:4d}  {SL.describe_key(k)}")
+    problems = _problems(case, batches)
+    assert not problems, "\n".join(problems)
+
+
+@pytest.mark.parametrize("case,batch,uncovers", [(("baseline", 64, "bf16"), 17, False), (("baseline", 64, "bf16"), 6, True),
+                                                 (("baseline", 64, "f32"), 33, True)])
+def test_coverage_condition_notices_a_dropped_batch(case, batch, uncovers):
+    """Without one of its required batches a list no longer satisfies the condition of the test above.  Without 6 (bf16) or 33
+    (f32) the census itself finds variant classes that nothing else reaches.  Without 17 it does not: every class 17 produces is
+    also produced by another batch of the list (test_variant_key_drops_the_batch_and_keeps_the_plan shows that 16 and 17 differ),
+    and 17 stays in the list only because the rules of the case require both sides of the split-K step -- that case shows no
+    more than that the required batches are enforced."""
+    rest = tuple(b for b in SL.OFF_BENCH_BATCHES[case] if b != batch)
+    problems = _problems(case, rest)
+    print(f"\n  without B={batch}: " + "; ".join(problems))
+    assert any(p.startswith("required batches missing") for p in problems)
+    assert any("no tested batch produces" in p for p in problems) == uncovers
+
+
+def test_variant_key_drops_the_batch_and_keeps_the_plan():
+    """two batches on the same side of every threshold give one key set; a split-K step gives another"""
+    c = SL.Census("baseline", 64, "bf16")
+    k = {B: c.variant_keys(B) for B in (40, 56, 16, 17)}
+    assert k[40] == k[56], "batches 40 and 56 (both N % 8 == 0, between the split-K steps at 32 and 64) differ"
+    assert k[16] != k[17], "the split-K target step at B <= 16 changes no variant key"
+    names = {key[0] for key in k[40]}
+    assert {"p2p_igemm", "p2p_wgemm", "p2p_wgrad_small", "p2p_norm_act_fwd", "p2p_norm_act_bwd", "p2p_conv_fewin"} <= names

@@ -17,6 +17,66 @@ store (every element no task covers keeps its sentinel), the masks bit for bit a
 task tables are copied from the engine while it is alive and re-issued as fresh tables over test-owned buffers.  Forms that no
 benchmarked step issues are re-issued with hand-written arguments (test_entry_points_no_benchmarked_step_issues), and
 test_one_keras_update_per_parameter_per_step checks that a replayed step moves every parameter by exactly one Adam step.
+
+Off-benchmark batches (test_every_launch_of_off_benchmark_steps_against_f64).  batch() has no drop_remainder and parallel.py
+puts a remainder on the earlier ranks, so a step can have any batch, and the batch picks the kernel.  What the ENGINE and the
+library's host queries pick (entry point, split-K, msplit, nsplit, statistics slots, block-resident / fused / strip / few-channel
+routes, N % ipt and N % 8 classes) is in the variant key (tests/step_launches.variant_key); tests/test_step_launches_cpu.py runs
+the engine's own step on device 'meta' for B = 1 .. 512 and asserts that step_launches.OFF_BENCH_BATCHES reaches every key found
+up to the cap.  What a LAUNCHER picks from N behind an unchanged argument list is listed here, with the batches at which it flips
+for the layer shapes of S = 64 (S = 128 in brackets where it differs) and the tested batch on either side ("above the cap": the
+flip is beyond the case's cap, the upper side is the benchmarked batch of c2 / c4 / c5):
+  brig.hip brig_plan     ntiles = ceil(N / ipt), ipt = 256 / (LH*LW)   partial last tile when N % ipt != 0: key class "N % ipt"; 6, 9 | 16, 32
+  brig.hip brig_plan     ntiles * nnt < 160 -> im2col route             in the key (brig_ok): three 16x16 layers flip at 80 (79 | 80) [S = 128: 20 (16 | 20)];
+                                                                        the fourth (op G 64 -> 128: ncols 128, cbw = 1 only, nnt = 1) at 160 and the
+                                                                        8x8 layers at 157 / 160, above the cap
+  brig.hip brig_plan     cbw = 1 while ntiles * (ncols / bn2) < 192     16x16 layers run cbw = 1 from 80 on and flip at 192: above the cap
+  igemm.hip igemm_bm     256-row tiles once ceil(M/256)*(ncols/128)*gz  4x4 layers 49..56, 8x8 layers 61..62, 2x2 layer from 65 on: 48 | 49, 61 | 63,
+                         >= 256 (M = N*LH*LW, gz = phases * splitk)     64 | 79; also behind p2p_igemm_stat_slots (in the key where statistics are fused)
+  igemm.hip pipe_try     kg2 (second wave splits K) while tiles <= 384  16x16 / 8x8 layers lose it at 49 and regain it with the next split-K step: 48 | 49, 63 | 64
+  igemm.hip igemm_launch bigM = M >= 131072 (64- / 32-column tiles)     p2p_igemm: N >= 128 on 32x32 maps, above the cap.  p2p_igemm_edge (f32 steps and the
+                                                                        indexed head): 64x64 maps at 32 (f32 16 | 33, indexed 31 | 32), 32x32 maps of 2N
+                                                                        images at 64 and of N images at 128: above the cap (c2-f32)
+  igemm.hip igemm_go     nst = 3 LDS stages while nblk <= 320 (nblk =   p2p_igemm, 64-column op-P 16x16 layers: 3 | 2 at 41 (33 | 48; f32 33 | 256)
+                         ceil(M / BM) * column tiles * gz) and          [S = 128, 32x32: 11 (9 | 15)]; f32 32 -> 128 on 32x32: 11 (8 | 16).  p2p_igemm_edge
+                         taps * C * esz >= 512, else 2                  (f32): 64x64 maps 11 (8 | 16), 32x32 of 2N images 21 (16 | 33), of N images 41
+                                                                        (33 | 256); indexed head (bf16) 11 (8 | 31)
+  igemm.hip igemm_common w_major = weight bytes > gathered input bytes  16x16 layers at 2 and 4 (1 | 2 | 6; histogram / indexed 1 | 2 | 4; f32 1 | 6)
+                         (16 * ncols * C against N * pixels * C)        [S = 128: 4 and 8 (2 | 4, 7 | 8)]; 8x8 op G 128 -> 256 at 16 (9 | 16), the other
+                                                                        8x8 layers at 32 (17 | 32; f32 16 | 33) [S = 128: 32 / 64 above the cap]; 4x4 op G
+                                                                        256 -> 512 at 128, the other 4x4 layers at 256: above the cap
+  igemm.hip stat_slots   M % bm, hw % bm                                in the key (layer_stat_slots): 6, 9 | 8, 16
+  norm_act.hip norm_bwd_reg_geom  widest CG with N * (C / CG) >= 512    C=256 8x8: 16, 32, 64, 128; C=128 16x16: 32, 64, 128, 256; C=64 32x32: 64, 128:
+                                                                        9 | 16, 17 | 32, 33 | 63 | 64; 128 and 256 above the cap
+  norm_act.hip fwd/bwd   grid ((N + 7) / 8) * 8 * (C / CG)              idle image slots when N % 8 != 0: key class "N % 8"; 6, 9 | 8, 16
+  norm_act.hip fwd       sp2 doubles while N * (C / CG) * sp2 < 2048    apply-only pass (statistics from the conv epilogue).  S = 64: only up6 (64x64, C = 32)
+                         and the split keeps >= prr pixels, sp2 <= 64   runs it below batch 256: sp2 64 | 32 at 64 (63 | 64), then 128, 256 above the cap.
+                                                                        [S = 128: 64x64 C = 64, 128x128 C = 32 flip at 64; the others later: above the cap]
+  norm_act.hip fwd/bwd   sp = 1 if N * sp * C * 8 > ws_bytes            never: the engine sizes ws for max(B, 2) * 16 * 1024 pairs
+  norm_act.hip bwd       narrow: N * (C / 32) >= 1024, nsplit > 1       C=256 8x8 from 128 on: above the cap
+  norm_act.hip small     grid ceil(N * (C / 8) << lgG / 256)            grid size only (maps of <= 16 pixels)
+  conv_strip.hip cs_plan blocks = min(N * LH / TH, 256)                 persistent workgroups walk several strips past N = 32 (TH = 4): 32 | 33
+  conv_fewin / fewout    fi_plan / fo_plan: N * (LH / TH) < 2^31        never at these sizes; grid size only (fewin_ok / fewout_ok are in the key)
+  wgrad_small.hip ws_plan  blocks = min(N * LH / TH, want), want 32..512 one strip per workgroup below, several above: between 4 and 64 by layer
+                                                                        (2 | 6 | 9 | 16 .. 64 | 79); wgrad_small > 0 is in the key
+  wgrad_small.hip ws_sum_split  doubles while colblocks * split < 512   follows blocks (above): 2 | 6 | 16 | 33 | 64
+                         and nslabs / (2 * split) >= 4
+  wgemm.hip wgemm_pipe_ok  M % 64, chunk % 64 (M = N*LH*LW / msplit)    1x1 .. 4x4 layers: 1, 2, 6, 9 (M % 64 != 0) | 16, 32, 64; msplit is in the key
+                         and 16 * (Cg/128) * (Cd/128) * msplit <= 448  follows msplit (in the key)
+  conv_direct.hip view_colsum  nb = ceil(M / chunk) partials            grid size only
+  hist.hip launch_hist_bwd3  nsplit (pixel partition of an image) doubles  S = 64: 8 below 64, 4 for 64 .. 127 (48 | 64), 2 for 128 .. 255, 1 from 256 (c3).
+                         while N * nsplit < 256 and H*W / (2 nsplit)    nsplit = 2 lies between the cap and c3: re-issued at N = 128 by DIRECT
+                         >= 512                                         (test_entry_points_no_benchmarked_step_issues).  [S = 128: 32 below 16, 16 for
+                                                                        16 .. 31 (15 | 16); 8, 4, 2 above the cap; 1 from 256 (c5)]
+  hist.hip fwd3 / points / hellinger_fwd   grid (N, ...)                grid size only
+  losses.hip tanh_l1_bwd, optim.hip pack / unpack   blocks = min(ceil(N*H*W / 256), 4096)   one element per thread up to N*H*W = 2^20, grid-stride loop beyond:
+                                                                        N > 256 at S = 64, N > 64 at S = 128: above the cap (upper side c5 only)
+  optim.hip dropout_mask  blocks = min(ceil(n / 8 / 256), 2048)         n = N * res^2 * C of one mask > 2^22: N > 256 at S = 64 [N > 64]: above the cap
+  softmax.hip softmax_cce  blocks = min(ceil(M / 16), MAX_BLOCKS)       not in the recorded steps (the indexed step fuses the head: head_softmax.hip)
+  head_softmax.hip, losses.hip forward, sprites.hip   N enters grid sizes (N * H / 4 workgroups; P2P_LOSS_BLOCKS fixed), workspace offsets and the
+                                                                        1 / (N ...) scales only
+The flip batches of the igemm.hip, norm_act.hip sp2 and hist.hip rows were computed from the launch arguments of the census with the
+launchers' formulas; those of the wgrad_small.hip and wgemm.hip rows by hand.
 """
 import ctypes as C
 import gc
@@ -50,16 +110,7 @@ OUT_OF_SCOPE = {
 }
 
 
-def _val(v):
-    """a recorded ctypes argument as a Python value (structures for byref arguments)"""
-    if v is None:
-        return None
-    obj = getattr(v, "_obj", None)
-    if obj is not None:
-        return obj
-    if isinstance(v, C._SimpleCData):
-        return v.value
-    return v
+_val, _esz, _decode, _signature = SL.val, SL.elem_size, SL.decode, SL.signature        # (shared with the host-only census)
 
 
 def _blocks():
@@ -74,21 +125,10 @@ def _blocks():
     return out
 
 
-def _coff(ptr, ld, esz, blocks):
-    """(channel offset, pixel index inside its image) of a view pointer, counted from the start of the allocation it points into.
-    The caller checks that the pixel index is the view's first interior pixel: the allocation then starts on the pixel grid of
-    the view and the channel offset is the one the engine used."""
-    for a, s in blocks:
-        if a <= ptr < a + s:
-            assert (ptr - a) % esz == 0, f"view pointer {ptr:#x} is not on an element boundary"
-            e = (ptr - a) // esz
-            return e % ld, e // ld
-    raise AssertionError(f"view pointer {ptr:#x} is in no allocation")
-
-
 # ---------------------------------------------------------------------------------------------------------------- harvest
 def _build(cfg, dtype_name):
-    model, B, S, lam_l1, lam_hist, palette = bench.CONFIGS[cfg]
+    """cfg: the name of a bench.CONFIGS entry, or a step description (model, B, S, lambda_l1, lambda_hist, palette) of its own"""
+    model, B, S, lam_l1, lam_hist, palette = bench.CONFIGS[cfg] if isinstance(cfg, str) else cfg
     dtype = L.BF16 if dtype_name == "bf16" else L.F32
     if model == "indexed":
         eng = E.Pix2PixEngine(1, 256, "softmax", S, dtype, device=U.DEV, seed=47)
@@ -99,59 +139,6 @@ def _build(cfg, dtype_name):
     src, tgt = bench.synthetic_batch(0, B, S, palette)
     src_d, tgt_d = torch.as_tensor(src).to(U.DEV), torch.as_tensor(tgt).to(U.DEV)
     return eng, lambda: eng.train_step_rgba(src_d, tgt_d, lam_l1, lam_hist, global_batch=B)
-
-
-def _esz(dtype):
-    return 2 if dtype == L.BF16 else 4
-
-
-def _view_desc(t, ld_esz, blocks):
-    esz = ld_esz
-    coff, pix = _coff(t.ptr, t.ld, esz, blocks)
-    return {"ptr": t.ptr, "img_stride": int(t.img_stride), "row_stride": int(t.row_stride), "ld": int(t.ld),
-            "align": t.ptr % 16, "coff": coff, "pix": pix % int(t.img_stride)}
-
-
-def _gsrc_desc(g, dtype, blocks):
-    esz = 4 if g.kind == 2 else _esz(dtype)
-    return {"kind": int(g.kind), "nslabs": int(g.nslabs), "slab_stride": int(g.slab_stride), "ld": int(g.ld),
-            "coff": int(g.coff), "align": g.ptr % 16 if g.ptr else 0}
-
-
-def _decode(name, args, blocks):
-    """(name, args) -> list of plain values: ints / floats, view and gsrc descriptions, 'null' / 'ptr' for pointers"""
-    types = L.SIGNATURES[name]
-    assert len(types) == len(args), name
-    vals = [_val(a) for a in args]
-    dtype = None
-    if name in ("p2p_igemm", "p2p_igemm_norm_act", "p2p_conv_strip"):
-        dtype = vals[1]
-    elif name in ("p2p_igemm_edge", "p2p_conv_fewin", "p2p_conv_fewin_actbwd", "p2p_conv_fewout"):
-        dtype = vals[2]
-    elif name in ("p2p_wgemm", "p2p_wgemm_edge", "p2p_wgrad_small", "p2p_norm_act_fwd", "p2p_norm_act_fwd_tail",
-                  "p2p_norm_act_bwd", "p2p_act_bwd", "p2p_rgbuv_points", "p2p_rgbuv_hist_fwd3", "p2p_rgbuv_hist_hellinger_bwd3",
-                  "p2p_head_dgrad", "p2p_head_softmax_cce", "p2p_bce_logits", "p2p_bce_logits_pad8", "p2p_tanh_l1_fwd",
-                  "p2p_tanh_l1_fwd_pair", "p2p_tanh_l1_bwd", "p2p_tanh_l1_bwd_pad8", "p2p_view_colsum", "p2p_pack_input",
-                  "p2p_pack_input_multi", "p2p_pack_pair", "p2p_pack_pair_idx", "p2p_unpack", "p2p_weight_prep", "p2p_weight_prep_pad",
-                  "p2p_weight_prep_batched", "p2p_adam_prep_batched"):
-        dtype = vals[0]
-    out = []
-    for t, v in zip(types, vals):
-        if t is L._TP and name == "p2p_pack_input_multi":          # an array of ndst views
-            out.append(("views", tuple(tuple(sorted((k, x) for k, x in _view_desc(d, _esz(dtype), blocks).items() if k != "ptr"))
-                                       for d in list(v)[:vals[8]])))
-        elif t is L._TP:
-            out.append(None if v is None else ("view", _view_desc(v, _esz(dtype), blocks)))
-        elif t is L._GP:
-            out.append(None if v is None else ("gsrc", _gsrc_desc(v, dtype, blocks)))
-        elif t is C.c_void_p:
-            p = v.value if isinstance(v, C.c_void_p) else v
-            out.append(None if not p else ("ptr", p % 16))
-        elif t is C.c_float:
-            out.append(float(v))
-        else:
-            out.append(int(v))
-    return out
 
 
 def _raw_ptr(v):
@@ -219,19 +206,9 @@ def _decode_device_args(eng, tables, name, args, dec):
     return dec
 
 
-def _signature(name, dec):
-    key = []
-    for d in dec:
-        if isinstance(d, tuple) and d[0] in ("view", "gsrc"):
-            key.append((d[0],) + tuple(sorted((k, v) for k, v in d[1].items() if k != "ptr")))
-        else:
-            key.append(d)
-    return (name,) + tuple(key[:-1])           # the last argument is the stream
-
-
 def harvest(cfg, dtype_name, fuse_adam=None):
-    """unique launch signatures of the recorded step of one bench config: {signature: (name, decoded args)}, and the raw count.
-    fuse_adam: the engine's switch if not None (bench.py runs the default)"""
+    """unique launch signatures of the recorded step of one bench config or step description (_build): {signature: (name, decoded
+    args)}, and the raw count.  fuse_adam: the engine's switch if not None (bench.py runs the default)"""
     eng, step = _build(cfg, dtype_name)
     if fuse_adam is not None:
         eng.fuse_adam = fuse_adam
@@ -1814,15 +1791,14 @@ def _reissue_one(name, dec, seed, kw):
 STEP_CASES = [(c, d, None) for c, d in CONFIGS] + [("c2", "bf16", True)]
 
 
-@pytest.mark.parametrize("cfg,dtype_name,fuse", STEP_CASES, ids=[f"{c}-{d}" + ("-fused-adam" if f else "") for c, d, f in STEP_CASES])
-def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name, fuse):
-    """fuse: also the step with Adam and the operand copies in one launch per part (p2p_adam_prep_batched on the G_head / G_rest /
-    D tables), the engine's other Adam path"""
+def _check_step(cfg, dtype_name, fuse, label):
+    """harvest the recorded step, refuse unknown entry points, re-issue every unique launch (NaN before, sentinel around, a second
+    launch bit-identical) against f64 with the per-family tolerances, print the table; returns the harvest"""
     uniq, names = harvest(cfg, dtype_name, fuse)
     if fuse:
         assert "p2p_adam_prep_batched" in names, "the fused-Adam step issues no p2p_adam_prep_batched"
     unknown = sorted({n for n in names if n not in CHECKERS and n not in OUT_OF_SCOPE})
-    assert not unknown, f"{cfg}: entry points neither re-issued nor listed as out of scope: {unknown}"
+    assert not unknown, f"{label}: entry points neither re-issued nor listed as out of scope: {unknown}"
     dtype = L.BF16 if dtype_name == "bf16" else L.F32
     table, failures = {}, []
     for k, (sig, (name, dec)) in enumerate(sorted(uniq.items(), key=lambda kv: repr(kv[0]))):
@@ -1838,20 +1814,46 @@ def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name, fuse)
             if not e < _tol(fam, dtype):
                 failures.append(f"{name} {[d for d in dec if not isinstance(d, tuple)][:12]}: {fam} error {e:.3g} >= {_tol(fam, dtype):.3g}")
         torch.cuda.empty_cache()
-    print(f"\n[{cfg} {dtype_name}{' fused Adam' if fuse else ''}] {len(names)} calls per step, {len(uniq)} unique re-issued launch signatures")
+    print(f"\n[{label} {dtype_name}{' fused Adam' if fuse else ''}] {len(names)} calls per step, {len(uniq)} unique re-issued launch signatures")
     print(f"  {'entry point':28s} {'launches':>8s}  worst error per family (tolerance)")
     for name in sorted(table):
         r = table[name]
         fams = ", ".join(f"{f} {e:.2e} ({_tol(f, dtype):.0e})" for f, e in sorted(r["worst"].items()))
         print(f"  {name:28s} {r['launches']:8d}  {fams}")
     assert not failures, "\n".join(failures)
-    assert table, f"{cfg}: no launch re-issued"
+    assert table, f"{label}: no launch re-issued"
+    return uniq
+
+
+@pytest.mark.parametrize("cfg,dtype_name,fuse", STEP_CASES, ids=[f"{c}-{d}" + ("-fused-adam" if f else "") for c, d, f in STEP_CASES])
+def test_every_launch_of_the_benchmarked_step_against_f64(cfg, dtype_name, fuse):
+    """fuse: also the step with Adam and the operand copies in one launch per part (p2p_adam_prep_batched on the G_head / G_rest /
+    D tables), the engine's other Adam path"""
+    _check_step(cfg, dtype_name, fuse, cfg)
+
+
+_CENSUS = {}
+
+
+@pytest.mark.parametrize("model,S,dtype_name,B", SL.OFF_BENCH_CASES, ids=[f"{m}-{s}-{d}-b{b}" for m, s, d, b in SL.OFF_BENCH_CASES])
+def test_every_launch_of_off_benchmark_steps_against_f64(model, S, dtype_name, B):
+    """The same check at the batches of step_launches.OFF_BENCH_CASES (module docstring: chosen so that every kernel variant the
+    engine picks at or below the cap is re-issued at a batch that picks it).  The variant keys of the recorded step must be the
+    ones the host-only census gives for the batch: the census that chose the batches describes the engine that runs."""
+    uniq = _check_step(SL.step_desc(model, B, S), dtype_name, None, f"{model} {S}x{S} batch {B}")
+    case = (model, S, dtype_name)
+    if case not in _CENSUS:
+        _CENSUS[case] = SL.Census(*case)
+    got, want = SL.harvested_variant_keys(uniq), _CENSUS[case].variant_keys(B)
+    only_step = sorted(SL.describe_key(k) for k in got - want)
+    only_census = sorted(SL.describe_key(k) for k in want - got)
+    assert got == want, f"the census has drifted from the engine at batch {B}:\n  recorded step only: {only_step}\n  census only: {only_census}"
 
 
 def _direct_cases():
     """(name, dtype, decoded args) of the entry points and forms that no benchmarked step issues: the partial-store forms
     (P2P_FULL_PIXELS=0), generate() / hooked-step launches, the unbatched weight copies, the host-step Adam, an unaligned
-    dropout mask"""
+    dropout mask, the histogram backward at the one pixel partition no tested step reaches"""
     def v(*a, **k):
         return ("view", _vd(*a, **k))
     P, BF, F = ("ptr", 0), L.BF16, L.F32
@@ -1870,6 +1872,8 @@ def _direct_cases():
                                 None]),
         ("p2p_colsum", F, [P, 37, 19, 0.5, P, None]),
         ("p2p_hist_normalize", F, [P, 3, P, None]),
+        # launch_hist_bwd3's nsplit = 2 (N in 128 .. 255 at 64x64): above the cap of the off-benchmark steps, below c3's batch
+        ("p2p_rgbuv_hist_hellinger_bwd3", F, [F, 128, 64, 64, v(64, 64, 4), P, P, P, P, P, 1.0 / (2 * np.sqrt(2.0) * 128), P, P, None]),
         ("p2p_pack_pair", BF, [BF, 2, 8, 8, P, P, v(8, 8, 8, halo=1), v(8, 8, 40, halo=1, coff=32), v(8, 8, 8, halo=1),
                                v(8, 8, 8, halo=1), None]),
         ("p2p_pack_pair_idx", F, [F, 2, 8, 8, P, P, v(8, 8, 8, halo=1), v(8, 8, 40, halo=1, coff=32), v(8, 8, 8, halo=1),

@@ -277,6 +277,50 @@ def test_host_side_step_replay_is_bit_identical_to_eager_launching(kind, B):
     assert int(a.mask_counter_dev[0]) == int(b.mask_counter_dev[0])
 
 
+@pytest.mark.parametrize("dtype", [L.BF16, L.F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("kind", ["baseline", "indexed"])
+def test_an_epochs_ragged_batch_pattern_replays_bit_identically(kind, dtype):
+    """batch() has no drop_remainder (dataset_utils.py:137): 21 samples at batch 8 arrive as 8, 8, 5 every epoch.  Recordings are
+    keyed by batch and plans are kept per batch, while the parameter stores, Adam state, device step counters and the dropout
+    counter are shared.  Three epochs on a replaying engine and on one that launches eagerly, from the same weights and seed: the
+    first step of a batch size is eager, the second one is recorded, later ones are replayed -- both B = 8 steps of the second
+    epoch and every step of the third (B = 5 included) run through p2p_replay, interleaved with the other size.  Loss rows,
+    parameters, Adam moments, step counters and the mask counter are bit-identical after every step."""
+    from palette_and_histo_gan_amd import dataset_utils as DU
+    S, epochs = 64, 3
+    ds = (DU.synthetic_indexed_ds if kind == "indexed" else DU.synthetic_rgba_ds)(21, batch_size=8, seed=11)
+    batches = [b for _ in range(epochs) for b in ds]
+    assert [int(b[0].shape[0]) for b in batches] == [8, 8, 5] * epochs
+    engs, replayed = [], []
+    for replay in (True, False):
+        eng = E.Pix2PixEngine(1, 256, "softmax", S, dtype, seed=5) if kind == "indexed" else E.Pix2PixEngine(4, 4, "tanh", S, dtype, seed=5)
+        eng.replay_enabled = replay
+        engs.append(eng)
+    a, b = engs
+    orig = a._replay
+
+    def counting(key, *args, **kw):
+        replayed.append(len(rows))
+        return orig(key, *args, **kw)
+    a._replay = counting
+    rows = []
+    for t, bt in enumerate(batches):
+        if kind == "indexed":
+            la, lb = (e.train_step_indexed(bt[0], bt[1], 0.01) for e in engs)
+        else:
+            la, lb = (e.train_step_rgba(bt[0], bt[1], 100.0) for e in engs)
+        torch.cuda.synchronize()
+        rows.append(la)
+        assert torch.equal(la, lb), f"step {t + 1} (B={int(bt[0].shape[0])}): loss rows differ by {(la - lb).abs().max()}"
+        for sid, sa, sb in (("G", a.G, b.G), ("D", a.D, b.D)):
+            assert sa.t == sb.t == t + 1 and int(sa.t_dev[0]) == int(sb.t_dev[0]) == t + 1, f"step {t + 1}: {sid} step counters"
+            for buf in ("params", "m", "v"):
+                assert torch.equal(getattr(sa, buf), getattr(sb, buf)), f"step {t + 1} (B={int(bt[0].shape[0])}): {sid}.{buf}"
+        assert int(a.mask_counter_dev[0]) == int(b.mask_counter_dev[0]) == t + 1, f"step {t + 1}: mask counter"
+    assert replayed == [3, 4, 6, 7, 8], f"steps issued through p2p_replay (0-based): {replayed}"
+    assert len(a._replays) == 2 and len(b._replays) == 0
+
+
 @pytest.mark.parametrize("B,replay", [(4, True), (256, False), (256, True)])
 def test_forks_on_the_kernels_own_completion_signal_order_the_streams_like_event_records(B, replay):
     """Round 5: the weight-gradient forks behind p2p_norm_act_bwd / p2p_act_bwd ride on that kernel's own completion signal
