@@ -346,6 +346,29 @@ int p2p_rgbuv_hist_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, co
 int p2p_rgbuv_hist_general_bwd(int dtype, int N, int H, int W, const p2p_tensor* img, int size, int method, float sigma,
                                const float* gh, float* dimg, void* stream);
 
+/* ---- soft palette histogram and conformance (build-added, DESIGN.md "palette loss") ------------------------------ */
+/* f32 only; img: dense [N][H][W][4] in [-1, 1], 16-byte aligned, any H, W >= 1 (H * W <= 2^30, N <= 65535).  palette: int32
+ * [N][K][4] RGBA rows in 0..255, 16-byte aligned, K <= 256; sizes[n] = valid slots of image n (clamped to K; <= 0: the image
+ * contributes zeros).  With x_p = img_p * 0.5 + 0.5 (all four channels), c_k = palette[n][k] / 255 and tau > 0:
+ *   d_pk = sum_c (x_pc - c_kc)^2,   w_pk = exp(-(d_pk - min_j d_pj) / tau) / sum_j exp(-(d_pj - min_j d_pj) / tau)   (j, k < sizes[n])
+ *   hist[n][k] = (1 / HW) sum_p w_pk   (0 for k >= sizes[n]),      conf[n] = (1 / HW) sum_p sum_k w_pk d_pk.
+ * workspace: p2p_soft_palette_workspace_bytes(N, H, W) bytes of per-workgroup partial sums, added in workgroup order (no float
+ * atomics: bit-reproducible). */
+long long p2p_soft_palette_workspace_bytes(int N, int H, int W);
+int p2p_soft_palette_fwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                         float* hist, float* conf, float* workspace, void* stream);
+/* Its VJP for upstream gradients gh[N][K] and gm[N] (the weights are recomputed): with a_k = (gh_k + gm d_pk) / HW,
+ *   dL/dx_p = (2 / tau) sum_k w_pk (a_k - sum_j w_pj a_j) c_k + (2 gm / HW) (x_p - sum_k w_pk c_k),   dimg = 0.5 dL/dx,
+ * alpha included; dimg: dense f32 [N][H][W][4], 16-byte aligned, every pixel written.  The weighted differences are taken about
+ * the pixel's nearest slot, so they do not cancel where one colour dominates. */
+int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                         const float* gh, const float* gm, float* dimg, void* stream);
+/* Palette of every image: q = clamp(floor((img * 0.5 + 0.5) * 255 + 0.5), 0, 255) per channel (each step rounded to f32), key =
+ * r + 256 g + 65536 b + 2^24 a (unsigned); palette_out[n][0 .. sizes_out[n]) = the image's distinct keys in ascending order
+ * (transparent black first), unpacked to int32 RGBA, remaining rows 0.  More than `cap` (1..256) distinct colours:
+ * sizes_out[n] = -1 and a zeroed row.  One workgroup per image (LDS hash set, integer atomics, bounded probing). */
+int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* palette_out, int* sizes_out, void* stream);
+
 /* ---- palette-index head (pix2pix_model.py:261-325) ------------------------------------------------------------ */
 
 /* z: logits view [N][H][W][C]; target: view holding the real palette index of every pixel (as a value of `dtype`).

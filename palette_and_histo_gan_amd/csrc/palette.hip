@@ -1,0 +1,328 @@
+// Soft palette histogram and conformance of an RGBA image under a palette, their VJP, and the palette of an image
+// (DESIGN.md "palette loss").  With x_p = img_p * 0.5 + 0.5 (four channels), c_k = pal_k / 255 and n valid slots:
+//   d_pk = sum_c (x_pc - c_kc)^2,   w_pk = softmax_k(-(d_pk - min_j d_pj) / tau),
+//   h_k = mean_p w_pk,   m = mean_p sum_k w_pk d_pk.
+// Vector-ALU and exponential bound (H*W*K pair evaluations per image), no matrix work.  The image's palette sits in LDS as one
+// float4 per slot (4 KB); the slot loops read it at a wave-uniform address (broadcast, one ds_read_b128 per slot shared by the
+// lane's pixels); every lane owns its own pixels.  All reductions run in a fixed order (no float atomics): bit-reproducible.
+#include "p2p_common.hpp"
+
+#define PAL_MAX 256
+#define PAL_THREADS 256
+#define PAL_FWD_PIX 4                       // pixels per lane, forward
+#define PAL_BWD_PIX 2                       // pixels per lane, backward
+#define PAL_WS_STRIDE 260                   // floats per (image, chunk) partial: 256 slot sums, the conformance sum, padding
+
+__device__ __forceinline__ float pal_dist(const float4& x, const float4& c) {
+    const float dx = x.x - c.x, dy = x.y - c.y, dz = x.z - c.z, dw = x.w - c.w;
+    // spelled out: the passes over the slots must reproduce each other's d bit for bit (d - min is 0 at the nearest slot)
+    return __fmaf_rn(dw, dw, __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))));
+}
+
+__device__ __forceinline__ float4 pal_x(const float* __restrict__ img, long long pix) {
+    const float4 v = *(const float4*)(img + pix * 4);
+    return make_float4(__fmaf_rn(v.x, 0.5f, 0.5f), __fmaf_rn(v.y, 0.5f, 0.5f), __fmaf_rn(v.z, 0.5f, 0.5f), __fmaf_rn(v.w, 0.5f, 0.5f));
+}
+
+// the image's valid slots as float4 colours in LDS; returns their count (0: nothing to do)
+__device__ __forceinline__ int pal_load(const int* __restrict__ palette, const int* __restrict__ sizes, int b, int K, float4* c) {
+    int n = sizes[b];
+    n = n < 0 ? 0 : (n > K ? K : n);
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const int4 q = *(const int4*)(palette + ((long long)b * K + k) * 4);
+        c[k] = make_float4((float)q.x / 255.f, (float)q.y / 255.f, (float)q.z / 255.f, (float)q.w / 255.f);
+    }
+    __syncthreads();
+    return n;
+}
+
+// Forward, grid (chunks, N): a workgroup owns PAL_THREADS * PAL_FWD_PIX consecutive pixels of one image and writes the sums of
+// its pixels' weights per slot and of their conformance to ws[image][chunk][PAL_WS_STRIDE].
+//   pass 1: min_k d;  pass 2: S = sum_k e_k and sum_k e_k (d_k - min), e_k = exp2((d_k - min) * nscale), nscale = -log2(e) / tau;
+//   pass 3: per slot, e_k / S summed over the lane's pixels, across the wave (butterfly), then across the waves through LDS.
+__global__ __launch_bounds__(PAL_THREADS) void soft_palette_fwd_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                       const int* __restrict__ sizes, int K, float nscale,
+                                                                       float* __restrict__ ws) {
+    __shared__ float4 c[PAL_MAX];
+    __shared__ float part[PAL_THREADS / 64][PAL_MAX];
+    __shared__ float red[16];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* out = ws + ((long long)b * gridDim.x + blockIdx.x) * PAL_WS_STRIDE;
+    const int n = pal_load(palette, sizes, b, K, c);
+    if (n == 0) {                           // the whole workgroup: an image without a palette contributes nothing
+        for (int k = tid; k < PAL_WS_STRIDE; k += PAL_THREADS) out[k] = 0.f;
+        return;
+    }
+    float4 x[PAL_FWD_PIX];
+    float mn[PAL_FWD_PIX], inv[PAL_FWD_PIX];
+    bool valid[PAL_FWD_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_FWD_PIX; ++j) {
+        const int p = (blockIdx.x * PAL_FWD_PIX + j) * PAL_THREADS + tid;
+        valid[j] = p < HW;
+        x[j] = valid[j] ? pal_x(img, (long long)b * HW + p) : make_float4(0.f, 0.f, 0.f, 0.f);
+        mn[j] = INFINITY;
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_FWD_PIX; ++j) mn[j] = fminf(mn[j], pal_dist(x[j], ck));
+    }
+    float S[PAL_FWD_PIX], D[PAL_FWD_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_FWD_PIX; ++j) S[j] = D[j] = 0.f;
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_FWD_PIX; ++j) {
+            const float t = pal_dist(x[j], ck) - mn[j];
+            const float e = __builtin_amdgcn_exp2f(t * nscale);
+            S[j] += e;
+            D[j] = __fmaf_rn(e, t, D[j]);
+        }
+    }
+    float conf = 0.f;
+#pragma unroll
+    for (int j = 0; j < PAL_FWD_PIX; ++j) {
+        inv[j] = valid[j] ? 1.f / S[j] : 0.f;                 // S >= 1: the nearest slot contributes exp2(0)
+        conf += valid[j] ? mn[j] + D[j] * inv[j] : 0.f;       // sum_k w_k d_k = min + sum_k w_k (d_k - min)
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < PAL_FWD_PIX; ++j) {
+            const float t = pal_dist(x[j], ck) - mn[j];
+            acc = __fmaf_rn(__builtin_amdgcn_exp2f(t * nscale), inv[j], acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) part[wave][k] = acc;
+    }
+    __syncthreads();
+    for (int k = tid; k < PAL_MAX; k += PAL_THREADS) {
+        float s = 0.f;
+        if (k < n)
+            for (int w = 0; w < PAL_THREADS / 64; ++w) s += part[w][k];
+        out[k] = s;
+    }
+    conf = block_sum(conf, red);
+    if (tid == 0) out[PAL_MAX] = conf;
+}
+
+// hist[b][k] = (sum over the image's chunks, in chunk order) / HW; conf[b] likewise.  Grid N.
+__global__ __launch_bounds__(PAL_THREADS) void soft_palette_finish_kernel(int HW, int chunks, int K, const float* __restrict__ ws,
+                                                                          float* __restrict__ hist, float* __restrict__ conf) {
+    const int b = blockIdx.x;
+    const float* in = ws + (long long)b * chunks * PAL_WS_STRIDE;
+    for (int k = threadIdx.x; k <= PAL_MAX; k += PAL_THREADS) {
+        if (k >= K && k != PAL_MAX) continue;
+        float s = 0.f;
+        for (int ch = 0; ch < chunks; ++ch) s += in[(long long)ch * PAL_WS_STRIDE + k];
+        s = s / (float)HW;
+        if (k == PAL_MAX) conf[b] = s;
+        else hist[(long long)b * K + k] = s;
+    }
+}
+
+// VJP, grid (chunks, N), one dimg pixel per lane and step.  With r the nearest slot of the pixel, a_k = gh_k + gm d_k (times 1/HW)
+// and E[.] the mean under w:  sum_k w_k (a_k - E a) c_k = E[(a - a_r)(c - c_r)] - E[a - a_r] E[c - c_r]  -- the covariance taken
+// about slot r.  Where one colour dominates, a_k - E a cancels to rounding in f32; about r every term of the dominant slot is
+// exactly 0 and the rest is small times small, so no wide arithmetic is needed.  x - E c = (x - c_r) - E[c - c_r] likewise.
+//   pass 1: min_k d and its first index r;  pass 2: one exponential per pair and the ten running sums.
+__global__ __launch_bounds__(PAL_THREADS) void soft_palette_bwd_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                       const int* __restrict__ sizes, int K, float nscale, float two_over_tau,
+                                                                       const float* __restrict__ gh, const float* __restrict__ gm,
+                                                                       float* __restrict__ dimg) {
+    __shared__ float4 c[PAL_MAX];
+    __shared__ float g[PAL_MAX];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = pal_load(palette, sizes, b, K, c);
+    int pix[PAL_BWD_PIX];
+    bool valid[PAL_BWD_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_BWD_PIX; ++j) {
+        pix[j] = (blockIdx.x * PAL_BWD_PIX + j) * PAL_THREADS + tid;
+        valid[j] = pix[j] < HW;
+    }
+    if (n == 0) {
+#pragma unroll
+        for (int j = 0; j < PAL_BWD_PIX; ++j)
+            if (valid[j]) *(float4*)(dimg + ((long long)b * HW + pix[j]) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    for (int k = tid; k < n; k += PAL_THREADS) g[k] = gh[(long long)b * K + k];
+    __syncthreads();
+    const float gmb = gm[b];
+    float4 x[PAL_BWD_PIX];
+    float mn[PAL_BWD_PIX];
+    int r[PAL_BWD_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_BWD_PIX; ++j) {
+        x[j] = valid[j] ? pal_x(img, (long long)b * HW + pix[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        mn[j] = INFINITY;
+        r[j] = 0;
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_BWD_PIX; ++j) {
+            const float d = pal_dist(x[j], ck);
+            if (d < mn[j]) { mn[j] = d; r[j] = k; }
+        }
+    }
+    float4 cr[PAL_BWD_PIX], Ec[PAL_BWD_PIX], Eac[PAL_BWD_PIX];
+    float gr[PAL_BWD_PIX], S[PAL_BWD_PIX], Ea[PAL_BWD_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_BWD_PIX; ++j) {
+        cr[j] = c[r[j]];
+        gr[j] = g[r[j]];
+        S[j] = Ea[j] = 0.f;
+        Ec[j] = Eac[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+        const float gk = g[k];
+#pragma unroll
+        for (int j = 0; j < PAL_BWD_PIX; ++j) {
+            const float t = pal_dist(x[j], ck) - mn[j];
+            const float e = __builtin_amdgcn_exp2f(t * nscale);
+            const float ea = e * __fmaf_rn(gmb, t, gk - gr[j]);              // e (a_k - a_r), HW left out
+            const float cx = ck.x - cr[j].x, cy = ck.y - cr[j].y, cz = ck.z - cr[j].z, cw = ck.w - cr[j].w;
+            S[j] += e;
+            Ea[j] += ea;
+            Ec[j].x = __fmaf_rn(e, cx, Ec[j].x); Ec[j].y = __fmaf_rn(e, cy, Ec[j].y);
+            Ec[j].z = __fmaf_rn(e, cz, Ec[j].z); Ec[j].w = __fmaf_rn(e, cw, Ec[j].w);
+            Eac[j].x = __fmaf_rn(ea, cx, Eac[j].x); Eac[j].y = __fmaf_rn(ea, cy, Eac[j].y);
+            Eac[j].z = __fmaf_rn(ea, cz, Eac[j].z); Eac[j].w = __fmaf_rn(ea, cw, Eac[j].w);
+        }
+    }
+    const float inv_hw = 1.f / (float)HW;
+#pragma unroll
+    for (int j = 0; j < PAL_BWD_PIX; ++j) {
+        if (!valid[j]) continue;
+        const float is = 1.f / S[j];
+        const float ea = Ea[j] * is;
+        const float s1 = 0.5f * two_over_tau * inv_hw, s2 = gmb * inv_hw;    // 0.5: d x / d img
+        float4 o;
+        o.x = s1 * (Eac[j].x * is - ea * (Ec[j].x * is)) + s2 * ((x[j].x - cr[j].x) - Ec[j].x * is);
+        o.y = s1 * (Eac[j].y * is - ea * (Ec[j].y * is)) + s2 * ((x[j].y - cr[j].y) - Ec[j].y * is);
+        o.z = s1 * (Eac[j].z * is - ea * (Ec[j].z * is)) + s2 * ((x[j].z - cr[j].z) - Ec[j].z * is);
+        o.w = s1 * (Eac[j].w * is - ea * (Ec[j].w * is)) + s2 * ((x[j].w - cr[j].w) - Ec[j].w * is);
+        *(float4*)(dimg + ((long long)b * HW + pix[j]) * 4) = o;
+    }
+}
+
+// Palette of an image: its distinct quantised RGBA colours in ascending order of r + 256 g + 65536 b + 2^24 a.  One workgroup per
+// image: an open-addressing hash set in LDS (integer atomics only), then a rank sort of the occupied slots.  A slot is 64 bits wide
+// because every 32-bit value is a key (opaque white is 0xFFFFFFFF): EMPTY lies outside the key space.  More than `cap` colours:
+// size -1, zeroed row.  Every insertion past the cap raises `over`, which every lane reads before its next pixel, so at most
+// cap + PAL_THREADS keys are ever stored in the PAL_TABLE slots: a probe always finds a free slot, and is bounded by the table
+// size regardless.
+#define PAL_TABLE 1024
+#define PAL_EMPTY 0xFFFFFFFFFFFFFFFFull
+
+__device__ __forceinline__ unsigned pal_quant(float v) {
+    // clamp(floor((v * 0.5 + 0.5) * 255 + 0.5), 0, 255), every step rounded to f32 on its own
+    const float q = floorf(__fadd_rn(__fmul_rn(__fmaf_rn(v, 0.5f, 0.5f), 255.f), 0.5f));
+    return (unsigned)fminf(fmaxf(q, 0.f), 255.f);          // fmaxf(NaN, 0) = 0
+}
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_extract_kernel(int HW, const float* __restrict__ img, int cap, int* __restrict__ pal_out,
+                                                                      int* __restrict__ sizes_out) {
+    __shared__ unsigned long long table[PAL_TABLE];
+    __shared__ unsigned keys[PAL_MAX];
+    __shared__ int count, over, m;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < PAL_TABLE; i += PAL_THREADS) table[i] = PAL_EMPTY;
+    if (tid == 0) { count = 0; over = 0; m = 0; }
+    __syncthreads();
+    for (int p = tid; p < HW; p += PAL_THREADS) {
+        if (*(volatile int*)&over) break;
+        const float4 v = *(const float4*)(img + ((long long)b * HW + p) * 4);
+        const unsigned key = pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
+        unsigned slot = (key * 2654435761u) >> 22;          // Fibonacci hash, top 10 bits
+        for (int probe = 0; probe < PAL_TABLE; ++probe) {
+            const unsigned long long seen = atomicCAS(&table[slot], PAL_EMPTY, (unsigned long long)key);
+            if (seen == (unsigned long long)key) break;     // already there
+            if (seen == PAL_EMPTY) {                         // this lane inserted it
+                if (atomicAdd(&count, 1) + 1 > cap) atomicExch(&over, 1);
+                break;
+            }
+            slot = (slot + 1) & (PAL_TABLE - 1);
+        }
+    }
+    __syncthreads();
+    int* row = pal_out + (long long)b * cap * 4;
+    if (over) {
+        for (int i = tid; i < cap * 4; i += PAL_THREADS) row[i] = 0;
+        if (tid == 0) sizes_out[b] = -1;
+        return;
+    }
+    for (int i = tid; i < PAL_TABLE; i += PAL_THREADS) {
+        const unsigned long long e = table[i];
+        if (e != PAL_EMPTY) {
+            const int at = atomicAdd(&m, 1);                  // any order: the ranks below do not depend on it
+            if (at < PAL_MAX) keys[at] = (unsigned)e;
+        }
+    }
+    __syncthreads();
+    const int n = m < cap ? m : cap;                         // m == count <= cap <= PAL_MAX here
+    for (int i = n + tid; i < cap; i += PAL_THREADS) *(int4*)(row + 4 * i) = make_int4(0, 0, 0, 0);
+    if (tid < n) {
+        const unsigned key = keys[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += keys[j] < key ? 1 : 0;      // keys are distinct
+        *(int4*)(row + 4 * rank) = make_int4((int)(key & 255u), (int)((key >> 8) & 255u), (int)((key >> 16) & 255u), (int)(key >> 24));
+    }
+    if (tid == 0) sizes_out[b] = n;
+}
+
+static inline int pal_chunks(int H, int W, int per_lane) {
+    const long long per = (long long)PAL_THREADS * per_lane;
+    return (int)(((long long)H * W + per - 1) / per);
+}
+
+static int pal_check(const char* who, int N, int H, int W, const void* img, const void* palette, const void* sizes, int K, float tau) {
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0 && (long long)H * W <= (1LL << 30) && N <= 65535, "%s: bad shape %d x %d x %d (H * W <= 2^30, N <= 65535)", who, N, H, W);
+    P2P_REQUIRE(K >= 1 && K <= PAL_MAX, "%s: K = %d, a palette has 1..%d slots", who, K, PAL_MAX);
+    P2P_REQUIRE(tau >= 1e-30f && tau <= 3.0e38f, "%s: the temperature must be positive and finite (>= 1e-30)", who);
+    P2P_REQUIRE(img && palette && sizes, "%s: null pointer", who);
+    P2P_REQUIRE(((uintptr_t)img % 16) == 0 && ((uintptr_t)palette % 16) == 0, "%s: img and palette must be 16-byte aligned", who);
+    return 0;
+}
+
+extern "C" long long p2p_soft_palette_workspace_bytes(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return (long long)N * pal_chunks(H, W, PAL_FWD_PIX) * PAL_WS_STRIDE * (long long)sizeof(float);
+}
+
+extern "C" int p2p_soft_palette_fwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                                    float* hist, float* conf, float* workspace, void* stream) {
+    if (pal_check("p2p_soft_palette_fwd", N, H, W, img, palette, sizes, K, tau)) return -1;
+    P2P_REQUIRE(hist && conf && workspace, "p2p_soft_palette_fwd: null pointer");
+    const int chunks = pal_chunks(H, W, PAL_FWD_PIX);
+    hipStream_t st = (hipStream_t)stream;
+    const float nscale = (float)(-1.4426950408889634 / (double)tau);
+    soft_palette_fwd_kernel<<<dim3(chunks, N), PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, nscale, workspace);
+    soft_palette_finish_kernel<<<N, PAL_THREADS, 0, st>>>(H * W, chunks, K, workspace, hist, conf);
+    return p2p_check_launch("p2p_soft_palette_fwd");
+}
+
+extern "C" int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                                    const float* gh, const float* gm, float* dimg, void* stream) {
+    if (pal_check("p2p_soft_palette_bwd", N, H, W, img, palette, sizes, K, tau)) return -1;
+    P2P_REQUIRE(gh && gm && dimg && ((uintptr_t)dimg % 16) == 0, "p2p_soft_palette_bwd: null or unaligned pointer");
+    const float nscale = (float)(-1.4426950408889634 / (double)tau);
+    soft_palette_bwd_kernel<<<dim3(pal_chunks(H, W, PAL_BWD_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
+        H * W, img, palette, sizes, K, nscale, (float)(2.0 / (double)tau), gh, gm, dimg);
+    return p2p_check_launch("p2p_soft_palette_bwd");
+}
+
+extern "C" int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* palette_out, int* sizes_out, void* stream) {
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0 && (long long)H * W <= (1LL << 30), "p2p_palette_extract: bad shape %d x %d x %d", N, H, W);
+    P2P_REQUIRE(cap >= 1 && cap <= PAL_MAX, "p2p_palette_extract: cap = %d, a palette has 1..%d slots", cap, PAL_MAX);
+    P2P_REQUIRE(img && palette_out && sizes_out && ((uintptr_t)img % 16) == 0 && ((uintptr_t)palette_out % 16) == 0,
+                "p2p_palette_extract: null or unaligned pointer");
+    palette_extract_kernel<<<N, PAL_THREADS, 0, (hipStream_t)stream>>>(H * W, img, cap, palette_out, sizes_out);
+    return p2p_check_launch("p2p_palette_extract");
+}

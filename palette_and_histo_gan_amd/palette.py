@@ -1,0 +1,137 @@
+"""Soft palette histogram and palette conformance of RGBA images (build-added: the reference's histogram.py only has the RGB-uv
+histogram; DESIGN.md "palette loss" holds the definitions).
+
+`extract_palette_batch` finds every image's palette on the device (p2p_palette_extract), `soft_palette_histogram` measures how an
+image's pixels distribute over a palette's slots and how far they sit from them (p2p_soft_palette_fwd) and is differentiable with
+respect to the image: one torch.autograd.Function whose backward is HIP as well (p2p_soft_palette_bwd), so a loss hook of
+engine.train_step_rgba_hooked or a tf.GradientTape step written with it reaches the generator.  `palette_histogram_loss` is a
+handful of torch ops on the (B, K) result.  All kernels launch on the current stream; there is no CPU path.
+
+The default temperature 1e-3 makes a pixel that sits on a palette colour count for that slot alone (two colours one 8-bit step apart
+in one channel are 1.5e-5 apart in d, a weight ratio of 0.985; a pixel half-way between two clearly different colours is shared).
+It is a design choice: its effect on training quality has not been measured.
+"""
+import ctypes as C
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+from .configuration import MAX_PALETTE_SIZE
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _device_of(x, device):
+    if device is not None:
+        return torch.device(device)
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        return x.device
+    return torch.device("cuda:0")
+
+
+def _rgba(image_batch, dev):
+    """the kernels' input: a dense f32 (B, H, W, 4) device tensor (the conversion stays on the autograd graph)"""
+    img = torch.as_tensor(image_batch).to(device=dev, dtype=torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[3] != 4 or img.numel() == 0:
+        raise ValueError(f"expected a non-empty (B, H, W, 4) RGBA batch, got {tuple(img.shape)}")
+    return img
+
+
+def extract_palette_batch(images, check=True, device=None):
+    """Palettes of a (B, H, W, 4) batch in [-1, 1]: (palette int32 (B, 256, 4), sizes int32 (B,)) on the device.  Row b lists the
+    image's distinct 8-bit RGBA colours, clamp(floor((img * 0.5 + 0.5) * 255 + 0.5), 0, 255), in ascending order of
+    r + 256 g + 65536 b + 2^24 a -- transparent black first, as in the indexed pipeline -- followed by zero rows.  An image with
+    more than MAX_PALETTE_SIZE colours gets size -1 and a zeroed row; with `check` the sizes are read back (a host sync) and such
+    an image raises ValueError, without it nothing waits for the device."""
+    L.lib()
+    dev = _device_of(images, device)
+    img = _rgba(images, dev).detach()
+    B, H, W, _ = (int(x) for x in img.shape)
+    palette = torch.empty((B, MAX_PALETTE_SIZE, 4), dtype=torch.int32, device=dev)
+    sizes = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("p2p_palette_extract", B, H, W, _p(img), MAX_PALETTE_SIZE, _p(palette), _p(sizes), _stream(dev))
+    if check:
+        over = torch.nonzero(sizes < 0).flatten().tolist()
+        if over:
+            raise ValueError(f"image {over[0]} of the batch has more than {MAX_PALETTE_SIZE} distinct RGBA colours "
+                             f"({len(over)} of {B} images do)")
+    return palette, sizes
+
+
+class SoftPaletteHistogram(torch.autograd.Function):
+    """img: dense f32 (B, H, W, 4) device tensor; palette int32 (B, K, 4), sizes int32 (B,), both dense on img's device ->
+    (hist (B, K), conformance (B,)).  Backward: the gradient with respect to img only; single backward."""
+
+    @staticmethod
+    def forward(ctx, img, palette, sizes, tau):
+        B, H, W, _ = (int(x) for x in img.shape)
+        K = int(palette.shape[1])
+        dev = img.device
+        hist = torch.empty((B, K), dtype=torch.float32, device=dev)
+        conf = torch.empty((B,), dtype=torch.float32, device=dev)
+        ws = torch.empty(max(int(L.lib().p2p_soft_palette_workspace_bytes(B, H, W)) // 4, 1), dtype=torch.float32, device=dev)
+        L.call("p2p_soft_palette_fwd", B, H, W, _p(img), _p(palette), _p(sizes), K, tau, _p(hist), _p(conf), _p(ws), _stream(dev))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(img, palette, sizes)
+            ctx.tau = tau
+        return hist, conf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_hist, grad_conf):
+        img, palette, sizes = ctx.saved_tensors
+        B, H, W, _ = (int(x) for x in img.shape)
+        K = int(palette.shape[1])
+        dev = img.device
+        zeros = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.to(torch.float32).contiguous()  # noqa: E731
+        gh, gm = zeros(grad_hist, (B, K)), zeros(grad_conf, (B,))
+        dimg = torch.empty_like(img)
+        with torch.cuda.device(dev):
+            L.call("p2p_soft_palette_bwd", B, H, W, _p(img), _p(palette), _p(sizes), K, ctx.tau, _p(gh), _p(gm), _p(dimg), _stream(dev))
+        return dimg, None, None, None
+
+
+def soft_palette_histogram(image_batch, palette, sizes=None, temperature=1e-3, device=None):
+    """(hist (B, K), conformance (B,)) of a (B, H, W, 4) batch in [-1, 1] under per-image palettes (B, K, 4) of 0..255 RGBA rows,
+    K <= 256, of which the first sizes[b] are valid (None: all K).  With x = img * 0.5 + 0.5, c_k = palette_k / 255 and
+    d_pk = |x_p - c_k|^2 over the four channels, w_pk = softmax_k(-(d_pk - min_j d_pj) / temperature):
+        hist[b, k] = mean_p w_pk (0 for k >= sizes[b]; a row sums to 1),   conformance[b] = mean_p sum_k w_pk d_pk.
+    An image with sizes[b] <= 0 (extract_palette_batch's -1 included) contributes zeros and a zero gradient; a size above K counts
+    as K.  Differentiable with respect to `image_batch` only (the gradient has its shape, dtype and device)."""
+    L.lib()          # fail loudly if the HIP library is missing: there is no CPU path
+    dev = _device_of(image_batch, device)
+    img = _rgba(image_batch, dev)
+    B = int(img.shape[0])
+    pal = torch.as_tensor(palette)
+    if pal.dim() != 3 or pal.shape[0] != B or pal.shape[2] != 4 or not 1 <= pal.shape[1] <= MAX_PALETTE_SIZE:
+        raise ValueError(f"expected a ({B}, K <= {MAX_PALETTE_SIZE}, 4) palette for a batch of {B}, got {tuple(pal.shape)}")
+    temperature = float(temperature)
+    if not 0.0 < temperature < float("inf"):
+        raise ValueError(f"the temperature must be positive and finite, got {temperature}")
+    pal = pal.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if sizes is None:
+        sz = torch.full((B,), int(pal.shape[1]), dtype=torch.int32, device=dev)
+    else:
+        sz = torch.as_tensor(sizes)
+        if tuple(sz.shape) != (B,):
+            raise ValueError(f"expected {B} palette sizes, got shape {tuple(sz.shape)}")
+        sz = sz.detach().to(device=dev, dtype=torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        return SoftPaletteHistogram.apply(img, pal, sz, temperature)
+
+
+def palette_histogram_loss(h_true, h_pred):
+    """Total variation between palette histograms, batch mean of 0.5 sum_k |h_pred - h_true|: 0 for equal rows, 1 for rows on
+    disjoint slots.  (Not the Hellinger distance of the RGB-uv histogram: slots without mass are the rule here, and sqrt has no
+    finite gradient at 0.)"""
+    h_pred = torch.as_tensor(h_pred)
+    h_true = torch.as_tensor(h_true).to(device=h_pred.device, dtype=h_pred.dtype)
+    return 0.5 * (h_pred - h_true).abs().sum(-1).mean()

@@ -4,6 +4,7 @@
     Pix2PixAugmentedModel(same)                  -- augmentation lives in the dataset (pix2pix_model.py:232-234)
     Pix2PixHistogramModel(..., lambda_l1, lambda_histogram)
     Pix2PixIndexedModel(train_ds, test_ds, model_name, architecture_name, lambda_segmentation=0.5)
+    Pix2PixPaletteModel(..., lambda_l1, lambda_palette, lambda_conformance=0.0, temperature=1e-3)      -- build-added
 
 The constructor follows the reference's (pix2pix_model.py:12-36): create_generator() / create_discriminator() with the
 reference's builder signatures, `loss_object`, two Adam(0.0002, beta_1=0.5) optimizers, `checkpoint`,
@@ -30,6 +31,7 @@ import torch
 
 from . import _lib as L
 from . import histogram as _histogram  # noqa: F401  (module parity with the reference's `import histogram`)
+from . import palette as _palette
 from .configuration import IMG_SIZE, MAX_PALETTE_SIZE
 from .engine import Pix2PixEngine
 from .networks import PatchDiscriminator, UnetGenerator
@@ -345,6 +347,46 @@ class Pix2PixHistogramModel(Pix2PixAugmentedModel):
         """pix2pix_model.py:255-258"""
         super().log_generator_loss(g_loss[:3], step)
         self.summary_writer.scalar("generator/histogram_loss", g_loss[3], step)
+
+
+class Pix2PixPaletteModel(Pix2PixAugmentedModel):
+    """Build-added (no counterpart in the reference): an RGBA generator held to the target sprite's palette.  generator_loss adds
+    lambda_palette * the total variation between the soft palette histograms of the real and the generated image, both taken under
+    the REAL image's palette (palette.soft_palette_histogram), and lambda_conformance * the generated pixels' mean weighted squared
+    distance to that palette.  The palette is extracted on the device at every step (the dataset's augmentation changes the hues
+    per batch) without a host sync; an image with more than MAX_PALETTE_SIZE colours contributes nothing to either term.
+    The class overrides the loss hook, so train_step runs engine.train_step_rgba_hooked: one GPU, not replayed."""
+
+    def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, lambda_palette, lambda_conformance=0.0,
+                 temperature=1e-3, **kw):
+        super().__init__(train_ds, test_ds, model_name, architecture_name, lambda_l1, **kw)
+        if not 0.0 < float(temperature) < float("inf"):
+            raise ValueError(f"the temperature must be positive and finite, got {temperature}")
+        self.lambda_palette, self.lambda_conformance, self.temperature = lambda_palette, lambda_conformance, float(temperature)
+
+    def generator_loss(self, fake_predicted, fake_image, real_image):
+        fake = torch.as_tensor(fake_image)
+        real = torch.as_tensor(real_image).to(fake.device)
+        palette, sizes = _palette.extract_palette_batch(real, check=False)
+        real_histogram, _ = _palette.soft_palette_histogram(real, palette, sizes, self.temperature)
+        fake_histogram, fake_conformance = _palette.soft_palette_histogram(fake, palette, sizes, self.temperature)
+        palette_loss = _palette.palette_histogram_loss(real_histogram, fake_histogram)
+        total_loss, adversarial_loss, l1_loss = super().generator_loss(fake_predicted, fake_image, real_image)
+        total_loss = total_loss + self.lambda_palette * palette_loss + self.lambda_conformance * fake_conformance.mean()
+        return total_loss, adversarial_loss, l1_loss, palette_loss
+
+    def train_step(self, batch, step, update_steps):
+        self._check_hooks()
+        source_image, real_image = batch
+        (src, real), Bg, lo, dp = self._shard(batch, [source_image, real_image])
+        out = self.engine.train_step_rgba_hooked(src, real, self.generator_loss, self.discriminator_loss)
+        g_loss, d_loss = (out[0], out[1], out[2], out[3]), (out[4], out[5], out[6])
+        self._log(g_loss, d_loss, step, update_steps)
+        return g_loss, d_loss
+
+    def log_generator_loss(self, g_loss, step):
+        super().log_generator_loss(g_loss[:3], step)
+        self.summary_writer.scalar("generator/palette_loss", g_loss[3], step)
 
 
 class Pix2PixIndexedModel(Pix2PixModel):
