@@ -368,6 +368,16 @@ int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const int* palet
  * (transparent black first), unpacked to int32 RGBA, remaining rows 0.  More than `cap` (1..256) distinct colours:
  * sizes_out[n] = -1 and a zeroed row.  One workgroup per image (LDS hash set, integer atomics, bounded probing). */
 int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* palette_out, int* sizes_out, void* stream);
+/* Nearest palette slot of every pixel, in integers (DESIGN.md "palette snap").  img, palette, sizes as for the soft histogram.
+ * With q_p the pixel quantised per channel as p2p_palette_extract quantises it (NaN -> 0) and n = clamp(sizes[n], 0, K):
+ *   D_pk = sum_c (q_pc - palette[k][c])^2 (0..260100),   index_out[p] = argmin_{k < n} D_pk (ties: the lowest k),
+ *   dist_out[p] = D_p,index,   image_out[p] = palette[index] / 127.5f - 1.0f (two f32 operations; 16-byte aligned),
+ *   counts_out[n][k] = #{p : index = k} (0 for k >= n),   stats_out[n] = { #{p : dist > 0}, sum_p dist }.
+ * n = 0: index -1, dist 0, image_out = img bit for bit, counts and stats 0.  image_out and dist_out may be NULL; every element of
+ * every other output is written (the call clears counts_out and stats_out itself; integer atomics across workgroups, so two calls
+ * give identical bits).  No workspace, no allocation. */
+int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,
+                     float* image_out, int* dist_out, int* counts_out, long long* stats_out, void* stream);
 
 /* ---- palette-index head (pix2pix_model.py:261-325) ------------------------------------------------------------ */
 

@@ -5,6 +5,7 @@
 // Vector-ALU and exponential bound (H*W*K pair evaluations per image), no matrix work.  The image's palette sits in LDS as one
 // float4 per slot (4 KB); the slot loops read it at a wave-uniform address (broadcast, one ds_read_b128 per slot shared by the
 // lane's pixels); every lane owns its own pixels.  All reductions run in a fixed order (no float atomics): bit-reproducible.
+// p2p_palette_snap, further down, is the hard counterpart in integer arithmetic (nearest slot, lowest index on ties).
 #include "p2p_common.hpp"
 
 #define PAL_MAX 256
@@ -277,6 +278,105 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_extract_kernel(int HW, co
     if (tid == 0) sizes_out[b] = n;
 }
 
+// Hard counterpart of the soft histogram: every pixel's nearest palette slot, in integers (DESIGN.md "palette snap").  A pixel is
+// quantised with pal_quant and packed into one word q; a slot sits in LDS as its packed bytes c_k and the word
+// ((|c_k|^2 + PAL_SNAP_BIAS) << 8) | k.  key_pk = word_k - (dot4(q, c_k) << 9) is ((|c_k|^2 - 2 q.c_k + BIAS) << 8) | k: the bias
+// 2 * 4 * 255^2 keeps the score non-negative (it is at most 3 * 4 * 255^2 = 780300 < 2^20, so the shifted score fits 28 bits), and
+// one unsigned min over k yields the nearest slot and, among equals, the lowest k.  dist = (key >> 8) - BIAS + |q|^2.
+// Grid (chunks, N): a workgroup owns PAL_THREADS * PAL_SNAP_PIX consecutive pixels of one image, counts its pixels per slot in LDS
+// and adds the non-zero counts and its two sums to global memory with integer atomics (any order gives the same bits);
+// palette_snap_clear_kernel zeroes those outputs first.
+#define PAL_SNAP_PIX 4
+#define PAL_SNAP_BIAS 520200u
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_snap_clear_kernel(long long n_counts, int* __restrict__ counts, long long n_stats,
+                                                                         long long* __restrict__ stats) {
+    const long long i = (long long)blockIdx.x * PAL_THREADS + threadIdx.x;
+    if (i < n_counts) counts[i] = 0;
+    if (i < n_stats) stats[i] = 0;
+}
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                   const int* __restrict__ sizes, int K, int* __restrict__ index_out,
+                                                                   float* __restrict__ image_out, int* __restrict__ dist_out,
+                                                                   int* __restrict__ counts, long long* __restrict__ stats) {
+    __shared__ uint2 slot[PAL_MAX];          // x: packed bytes, y: key word
+    __shared__ int cnt[PAL_MAX];
+    __shared__ unsigned sums[2];             // off-palette pixels and summed distances of the workgroup (<= 1024 * 260100 < 2^32)
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int n = sizes[b];
+    n = n < 0 ? 0 : (n > K ? K : n);
+    for (int k = tid; k < n; k += PAL_THREADS) {
+        const int4 c = *(const int4*)(palette + ((long long)b * K + k) * 4);
+        const unsigned cx = (unsigned)c.x & 255u, cy = (unsigned)c.y & 255u, cz = (unsigned)c.z & 255u, cw = (unsigned)c.w & 255u;
+        const unsigned pk = cx | (cy << 8) | (cz << 16) | (cw << 24);
+        slot[k] = make_uint2(pk, ((cx * cx + cy * cy + cz * cz + cw * cw + PAL_SNAP_BIAS) << 8) | (unsigned)k);
+        cnt[k] = 0;
+    }
+    if (tid < 2) sums[tid] = 0u;
+    __syncthreads();
+    const long long base = (long long)b * HW;
+    unsigned q[PAL_SNAP_PIX], key[PAL_SNAP_PIX];
+    bool valid[PAL_SNAP_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_SNAP_PIX; ++j) {
+        const int p = (blockIdx.x * PAL_SNAP_PIX + j) * PAL_THREADS + tid;
+        valid[j] = p < HW;
+        q[j] = 0u;
+        key[j] = 0xFFFFFFFFu;
+        if (!valid[j]) continue;
+        const float4 v = *(const float4*)(img + (base + p) * 4);
+        if (n == 0) {                        // nothing to snap to: the pixel passes through bit for bit
+            index_out[base + p] = -1;
+            if (dist_out) dist_out[base + p] = 0;
+            if (image_out) *(float4*)(image_out + (base + p) * 4) = v;
+        }
+        q[j] = pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
+    }
+    if (n == 0) return;                      // the whole workgroup; counts and stats stay 0
+#pragma unroll 4
+    for (int k = 0; k < n; ++k) {
+        const uint2 s = slot[k];             // wave-uniform address: one broadcast ds_read_b64 for the lane's pixels
+#pragma unroll
+        for (int j = 0; j < PAL_SNAP_PIX; ++j) {
+            const unsigned k2 = s.y - (__builtin_amdgcn_udot4(q[j], s.x, 0u, false) << 9);
+            key[j] = k2 < key[j] ? k2 : key[j];
+        }
+    }
+    unsigned off = 0u, dsum = 0u;
+#pragma unroll
+    for (int j = 0; j < PAL_SNAP_PIX; ++j) {
+        if (!valid[j]) continue;
+        const int p = (blockIdx.x * PAL_SNAP_PIX + j) * PAL_THREADS + tid;
+        const int idx = (int)(key[j] & 255u);
+        const unsigned d = (key[j] >> 8) - PAL_SNAP_BIAS + __builtin_amdgcn_udot4(q[j], q[j], 0u, false);
+        index_out[base + p] = idx;
+        if (dist_out) dist_out[base + p] = (int)d;
+        if (image_out) {
+            const unsigned c = slot[idx].x;
+            *(float4*)(image_out + (base + p) * 4) =
+                make_float4(__fsub_rn(__fdiv_rn((float)(c & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)((c >> 8) & 255u), 127.5f), 1.0f),
+                            __fsub_rn(__fdiv_rn((float)((c >> 16) & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)(c >> 24), 127.5f), 1.0f));
+        }
+        atomicAdd(&cnt[idx], 1);
+        off += d > 0u ? 1u : 0u;
+        dsum += d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        off += __shfl_xor(off, o, 64);
+        dsum += __shfl_xor(dsum, o, 64);
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(&sums[0], off);
+        atomicAdd(&sums[1], dsum);
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += PAL_THREADS)
+        if (cnt[k]) atomicAdd(counts + (long long)b * K + k, cnt[k]);
+    if (tid < 2 && sums[tid]) atomicAdd((unsigned long long*)(stats + (long long)b * 2 + tid), (unsigned long long)sums[tid]);
+}
+
 static inline int pal_chunks(int H, int W, int per_lane) {
     const long long per = (long long)PAL_THREADS * per_lane;
     return (int)(((long long)H * W + per - 1) / per);
@@ -316,6 +416,20 @@ extern "C" int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const
     soft_palette_bwd_kernel<<<dim3(pal_chunks(H, W, PAL_BWD_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
         H * W, img, palette, sizes, K, nscale, (float)(2.0 / (double)tau), gh, gm, dimg);
     return p2p_check_launch("p2p_soft_palette_bwd");
+}
+
+extern "C" int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,
+                                float* image_out, int* dist_out, int* counts_out, long long* stats_out, void* stream) {
+    if (pal_check("p2p_palette_snap", N, H, W, img, palette, sizes, K, 1.f)) return -1;
+    P2P_REQUIRE(index_out && counts_out && stats_out, "p2p_palette_snap: null pointer");
+    P2P_REQUIRE(((uintptr_t)image_out % 16) == 0, "p2p_palette_snap: image_out must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const long long n_counts = (long long)N * K, n_stats = (long long)N * 2;
+    const long long n_clear = n_counts > n_stats ? n_counts : n_stats;          // K = 1: more stats than counts
+    palette_snap_clear_kernel<<<(int)((n_clear + PAL_THREADS - 1) / PAL_THREADS), PAL_THREADS, 0, st>>>(n_counts, counts_out, n_stats, stats_out);
+    palette_snap_kernel<<<dim3(pal_chunks(H, W, PAL_SNAP_PIX), N), PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, index_out, image_out,
+                                                                                          dist_out, counts_out, stats_out);
+    return p2p_check_launch("p2p_palette_snap");
 }
 
 extern "C" int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* palette_out, int* sizes_out, void* stream) {

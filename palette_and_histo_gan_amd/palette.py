@@ -5,12 +5,17 @@ histogram; DESIGN.md "palette loss" holds the definitions).
 image's pixels distribute over a palette's slots and how far they sit from them (p2p_soft_palette_fwd) and is differentiable with
 respect to the image: one torch.autograd.Function whose backward is HIP as well (p2p_soft_palette_bwd), so a loss hook of
 engine.train_step_rgba_hooked or a tf.GradientTape step written with it reaches the generator.  `palette_histogram_loss` is a
-handful of torch ops on the (B, K) result.  All kernels launch on the current stream; there is no CPU path.
+handful of torch ops on the (B, K) result.  `snap_to_palette` is the hard counterpart (p2p_palette_snap: every pixel's nearest
+palette colour in exact integer arithmetic, per-slot counts, off-palette pixels), not differentiable, for inference
+(Pix2PixModel.generate(snap=)) and evaluation (`palette_metrics`, S2SModel.report_palette).  All kernels launch on the current
+stream; there is no CPU path.
 
 The default temperature 1e-3 makes a pixel that sits on a palette colour count for that slot alone (two colours one 8-bit step apart
 in one channel are 1.5e-5 apart in d, a weight ratio of 0.985; a pixel half-way between two clearly different colours is shared).
-It is a design choice: its effect on training quality has not been measured.
+It is a design choice: on synthetic pairs neither 1e-3 nor 5e-2 changed the trained model's L1 or its share of off-palette
+pixels by a resolved amount at lambda_palette = 1 (tools/quality_run.py --palette).
 """
+import collections
 import ctypes as C
 
 import torch
@@ -99,6 +104,26 @@ class SoftPaletteHistogram(torch.autograd.Function):
         return dimg, None, None, None
 
 
+def _checked_palette(palette, B):
+    pal = torch.as_tensor(palette)
+    if pal.dim() != 3 or pal.shape[0] != B or pal.shape[2] != 4 or not 1 <= pal.shape[1] <= MAX_PALETTE_SIZE:
+        raise ValueError(f"expected a ({B}, K <= {MAX_PALETTE_SIZE}, 4) palette for a batch of {B}, got {tuple(pal.shape)}")
+    return pal
+
+
+def _palette_args(pal, sizes, B, dev):
+    """the kernels' palette (B, K, 4) and sizes (B,) as dense int32 device tensors, from a checked palette"""
+    pal = pal.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if sizes is None:
+        sz = torch.full((B,), int(pal.shape[1]), dtype=torch.int32, device=dev)
+    else:
+        sz = torch.as_tensor(sizes)
+        if tuple(sz.shape) != (B,):
+            raise ValueError(f"expected {B} palette sizes, got shape {tuple(sz.shape)}")
+        sz = sz.detach().to(device=dev, dtype=torch.int32).contiguous()
+    return pal, sz
+
+
 def soft_palette_histogram(image_batch, palette, sizes=None, temperature=1e-3, device=None):
     """(hist (B, K), conformance (B,)) of a (B, H, W, 4) batch in [-1, 1] under per-image palettes (B, K, 4) of 0..255 RGBA rows,
     K <= 256, of which the first sizes[b] are valid (None: all K).  With x = img * 0.5 + 0.5, c_k = palette_k / 255 and
@@ -110,22 +135,68 @@ def soft_palette_histogram(image_batch, palette, sizes=None, temperature=1e-3, d
     dev = _device_of(image_batch, device)
     img = _rgba(image_batch, dev)
     B = int(img.shape[0])
-    pal = torch.as_tensor(palette)
-    if pal.dim() != 3 or pal.shape[0] != B or pal.shape[2] != 4 or not 1 <= pal.shape[1] <= MAX_PALETTE_SIZE:
-        raise ValueError(f"expected a ({B}, K <= {MAX_PALETTE_SIZE}, 4) palette for a batch of {B}, got {tuple(pal.shape)}")
+    pal = _checked_palette(palette, B)
     temperature = float(temperature)
     if not 0.0 < temperature < float("inf"):
         raise ValueError(f"the temperature must be positive and finite, got {temperature}")
-    pal = pal.detach().to(device=dev, dtype=torch.int32).contiguous()
-    if sizes is None:
-        sz = torch.full((B,), int(pal.shape[1]), dtype=torch.int32, device=dev)
-    else:
-        sz = torch.as_tensor(sizes)
-        if tuple(sz.shape) != (B,):
-            raise ValueError(f"expected {B} palette sizes, got shape {tuple(sz.shape)}")
-        sz = sz.detach().to(device=dev, dtype=torch.int32).contiguous()
+    pal, sz = _palette_args(pal, sizes, B, dev)
     with torch.cuda.device(dev):
         return SoftPaletteHistogram.apply(img, pal, sz, temperature)
+
+
+PaletteSnap = collections.namedtuple("PaletteSnap", "index image distance counts off_palette distance_sum")
+
+
+def snap_to_palette(image_batch, palette, sizes=None, device=None):
+    """Every pixel of a (B, H, W, 4) batch in [-1, 1] moved to the nearest colour of its image's palette (B, K <= 256, 4) of 0..255
+    RGBA rows, of which the first sizes[b] are valid (None: all K) -- the hard counterpart of soft_palette_histogram, in exact
+    integer arithmetic (p2p_palette_snap, DESIGN.md "palette snap").  With q_p the pixel quantised as extract_palette_batch
+    quantises it and D_pk = sum_c (q_pc - palette_kc)^2, returns PaletteSnap of device tensors:
+        index (B, H, W) int32         argmin_k D_pk, ties to the lowest k
+        image (B, H, W, 4) float32    palette[index] / 127.5 - 1 (the dataset's normalisation: snapping twice changes nothing)
+        distance (B, H, W) int32      D at the index, 0..260100
+        counts (B, K) int32           pixels per slot, 0 for k >= sizes[b]
+        off_palette (B,) int64        pixels with distance > 0
+        distance_sum (B,) int64       sum of distance
+    An image with sizes[b] <= 0 (extract_palette_batch's -1 included) has nothing to snap to: index -1, distance 0, its pixels
+    copied, zero counts and sums.  NOT differentiable: an argmin has no gradient; all outputs are detached."""
+    L.lib()          # fail loudly if the HIP library is missing: there is no CPU path
+    dev = _device_of(image_batch, device)
+    img = _rgba(image_batch, dev).detach()
+    B, H, W, _ = (int(x) for x in img.shape)
+    pal, sz = _palette_args(_checked_palette(palette, B), sizes, B, dev)
+    K = int(pal.shape[1])
+    index = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    image = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+    distance = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, K), dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.call("p2p_palette_snap", B, H, W, _p(img), _p(pal), _p(sz), K, _p(index), _p(image), _p(distance), _p(counts), _p(stats),
+               _stream(dev))
+    return PaletteSnap(index, image, distance, counts, stats[:, 0], stats[:, 1])
+
+
+def palette_metrics(fake_images, real_images, device=None):
+    """How far a generated batch strays from the palette of its target batch (both (B, H, W, 4) in [-1, 1]).  The palette of every
+    real image is extracted on the device (no host sync) and both batches are snapped to it.  A dict of (B,) device tensors:
+        off_palette    share of the fake image's pixels that are not a palette colour (distance > 0)
+        rms_distance   sqrt(distance_sum / (HW * 4)) / 255: the fake pixels' RMS channel distance to their nearest colour, in [0, 1]
+        histogram_tv   0.5 sum_k |counts_fake - counts_real| / HW: total variation between the two images' use of the palette
+        valid          bool, False for a real image with more than MAX_PALETTE_SIZE colours (its other entries are 0 and NaN-free)
+    Leave the images that are not `valid` out of any mean."""
+    dev = _device_of(fake_images, device)
+    real = _rgba(real_images, dev).detach()
+    fake = _rgba(fake_images, dev).detach()
+    if fake.shape != real.shape:
+        raise ValueError(f"expected two batches of one shape, got {tuple(fake.shape)} and {tuple(real.shape)}")
+    palette, sizes = extract_palette_batch(real, check=False, device=dev)
+    f, r = snap_to_palette(fake, palette, sizes, device=dev), snap_to_palette(real, palette, sizes, device=dev)
+    hw = float(real.shape[1] * real.shape[2])
+    return {"off_palette": f.off_palette.to(torch.float32) / hw,
+            "rms_distance": (torch.sqrt(f.distance_sum.to(torch.float64) / (hw * 4.0)) / 255.0).to(torch.float32),      # rounded to f32 once
+            "histogram_tv": 0.5 * (f.counts - r.counts).abs().sum(-1).to(torch.float32) / hw,
+            "valid": sizes > 0}
 
 
 def palette_histogram_loss(h_true, h_pred):

@@ -201,10 +201,23 @@ class Pix2PixModel(S2SModel):
         total_loss = fake_loss + real_loss
         return total_loss, real_loss, fake_loss
 
-    def generate(self, batch):
-        """pix2pix_model.py:58-60"""
-        source_image, _ = batch
-        return self.generator(source_image, training=True)
+    def generate(self, batch, snap=None):
+        """pix2pix_model.py:58-60.  `snap` (build-added) moves every generated pixel to the nearest colour of a palette
+        (palette.snap_to_palette, f32 result, not differentiable): "target" / "source" use the palette extracted from that image
+        of the batch on the device (an image with more than MAX_PALETTE_SIZE colours is returned as generated), a
+        (palette (B, K, 4), sizes (B,) or None) pair is used as given; None returns the generator's output unchanged."""
+        source_image, target_image = batch
+        fake_image = self.generator(source_image, training=True)
+        if snap is None:
+            return fake_image
+        if isinstance(snap, str):
+            if snap not in ("target", "source"):
+                raise ValueError(f'snap is None, "target", "source" or a (palette, sizes) pair, got {snap!r}')
+            palette, sizes = _palette.extract_palette_batch(target_image if snap == "target" else source_image, check=False,
+                                                            device=fake_image.device)
+        else:
+            palette, sizes = snap
+        return _palette.snap_to_palette(fake_image, palette, sizes, device=fake_image.device).image
 
     # -- the hot path ----------------------------------------------------------------------------------------------
     def _check_hooks(self):

@@ -235,6 +235,13 @@ class S2SModel(ABC):
                 if "evaluate_l1" in callbacks:
                     l1_train, l1_test = self.report_l1(step=(step + 1) // update_steps)
                     print(f" L1: {float(l1_train):.5f} / {float(l1_test):.5f} (train/test)")
+                if "evaluate_palette" in callbacks:
+                    if self._has_indexed_batches():
+                        print(" Palette: skipped (the indexed model is on-palette by construction)")
+                    else:
+                        p_train, p_test = self.report_palette(step=(step + 1) // update_steps)
+                        print(f" Palette: off {p_train['off_palette']:.5f} / {p_test['off_palette']:.5f}, "
+                              f"tv {p_train['histogram_tv']:.5f} / {p_test['histogram_tv']:.5f} (train/test)")
                 if "evaluate_fid" in callbacks:
                     from . import frechet_inception_distance as fid
                     if fid.configured_weights() is None:
@@ -388,6 +395,38 @@ class S2SModel(ABC):
         if self.summary_writer is not None and step is not None:
             self.summary_writer.scalar("fid/train", train_value, step)
             self.summary_writer.scalar("fid/test", test_value, step)
+        return train_value, test_value
+
+    def _has_indexed_batches(self):
+        """whether the datasets yield (source_idx, target_idx, palette) batches: such a model is on-palette by construction"""
+        for batch in self._whole(self.train_ds).unbatch().take(1).batch(1):
+            return len(batch) == 3
+        return False
+
+    def evaluate_palette(self, real_images, fake_images):
+        """build-added: means over the valid images of palette.palette_metrics (off_palette, rms_distance, histogram_tv), as floats"""
+        from . import palette
+        m = palette.palette_metrics(fake_images, real_images, device=getattr(getattr(self, "engine", None), "device", None))
+        valid = m["valid"].to(torch.float32)
+        count = valid.sum().clamp(min=1.0)
+        means = torch.stack([(m[k] * valid).sum() / count for k in ("off_palette", "rms_distance", "histogram_tv")]).cpu()
+        return {k: float(v) for k, v in zip(("off_palette", "rms_distance", "histogram_tv"), means)}
+
+    def report_palette(self, num_images=TEST_SIZE, step=None):
+        """build-added, beside report_l1 and over the same samples: how far the generated images stray from their targets'
+        palettes (DESIGN.md "palette snap").  Returns (train, test) dicts of the means of off_palette (share of pixels that are no
+        palette colour), rms_distance and histogram_tv over the images whose target has a palette (at most 256 colours)."""
+        if self._has_indexed_batches():
+            raise NotImplementedError("on-palette by construction")
+        train_real_images, train_fake_images = self.select_examples_for_evaluation(num_images, self.train_ds)
+        test_real_images, test_fake_images = self.select_examples_for_evaluation(num_images, self.test_ds)
+        train_value = self.evaluate_palette(train_real_images, train_fake_images)
+        test_value = self.evaluate_palette(test_real_images, test_fake_images)
+        if self.summary_writer is not None and step is not None:
+            self.summary_writer.scalar("palette-off/train", train_value["off_palette"], step)
+            self.summary_writer.scalar("palette-off/test", test_value["off_palette"], step)
+            self.summary_writer.scalar("palette-tv/train", train_value["histogram_tv"], step)
+            self.summary_writer.scalar("palette-tv/test", test_value["histogram_tv"], step)
         return train_value, test_value
 
     def report_l1(self, num_images=TEST_SIZE, step=None):

@@ -9,6 +9,11 @@ characters with a learnable front -> right relation: a character is a palette pl
 same character drawn narrower, shifted, with the face parts repainted in the hair colour.  The published numbers are therefore
 not the yardstick here -- f32 mode is: the question this run answers is whether the bf16 storage mode (the benchmarked dtype)
 trains to the same quality as the f32 parity mode.   python tools/quality_run.py [--steps 10080] > gpurun_out/quality_run.json
+
+--palette adds a second leg: the plain RGBA model, Pix2PixPaletteModel with lambda_palette = 1 at temperatures 1e-3
+and 5e-2, and one with lambda_conformance = 1 alone, all bf16 on the same pairs, steps and seed, each reporting report_l1() and
+report_palette() (share of generated pixels off the target's palette, their RMS distance to it, histogram total variation).
+`--dtypes ""` runs that leg alone.
 """
 import argparse
 import contextlib
@@ -71,6 +76,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10080)          # ceil(250 / 4) * 160 (experiments.ipynb:268)
     ap.add_argument("--update-steps", type=int, default=252)
     ap.add_argument("--dtypes", default="f32,bf16")
+    ap.add_argument("--palette", action="store_true", help="also train the four models of the palette-loss comparison")
     args = ap.parse_args()
     (tr_s, tr_t), (te_s, te_t) = make_sets()
     os.makedirs(os.path.join(ROOT, "gpurun_out", "quality"), exist_ok=True)
@@ -78,7 +84,7 @@ def main():
     out = {"recipe": {"model": "baseline (no aug.)", "lambda_l1": 100.0, "batch": 4, "train": 250, "test": 44, "steps": args.steps,
                       "data": "synthetic front -> right character pairs (tools/quality_run.py)"},
            "reference_published": {"l1_train": 0.00789, "l1_test": 0.06371, "note": "experiments.ipynb:372, RPG-Maker sprites, TF"}}
-    for name in args.dtypes.split(","):
+    for name in [n for n in args.dtypes.split(",") if n]:
         train = D.SpriteRGBADataset(tr_s, tr_t, augment=False, batch_size=4, seed=47)
         test = D.SpriteRGBADataset(te_s, te_t, augment=False, batch_size=4, seed=48)
         with contextlib.redirect_stdout(sys.stderr):
@@ -103,7 +109,37 @@ def main():
     if "f32" in out and "bf16" in out:
         out["bf16_vs_f32"] = {"l1_train_ratio": out["bf16"]["l1_train"] / out["f32"]["l1_train"],
                               "l1_test_ratio": out["bf16"]["l1_test"] / out["f32"]["l1_test"]}
+    if args.palette:
+        out["palette"] = palette_leg(args, (tr_s, tr_t), (te_s, te_t))
     print(json.dumps(out))
+
+
+PALETTE_RUNS = [("rgba", {}),
+                ("palette tau=1e-3", {"lambda_palette": 1.0, "temperature": 1e-3}),
+                ("palette tau=5e-2", {"lambda_palette": 1.0, "temperature": 5e-2}),
+                ("conformance tau=1e-3", {"lambda_palette": 0.0, "lambda_conformance": 1.0, "temperature": 1e-3})]
+
+
+def palette_leg(args, train_pairs, test_pairs):
+    """the four bf16 models of DESIGN.md 6c on the same pairs, steps and seed: report_l1() and report_palette() of each"""
+    res = {}
+    for name, kw in PALETTE_RUNS:
+        train = D.SpriteRGBADataset(*train_pairs, augment=False, batch_size=4, seed=47)
+        test = D.SpriteRGBADataset(*test_pairs, augment=False, batch_size=4, seed=48)
+        cls = M.Pix2PixPaletteModel if kw else M.Pix2PixModel
+        t0 = time.time()
+        with contextlib.redirect_stdout(sys.stderr):
+            model = cls(train, test, "front2right", "quality-" + name.replace(" ", "-"), lambda_l1=100.0, dtype="bf16", seed=47, **kw)
+            model.fit(args.steps, args.update_steps)
+            torch.cuda.synchronize()
+            wall = time.time() - t0
+            l1_train, l1_test = model.report_l1(44)
+            p_train, p_test = model.report_palette(44)
+        res[name] = {"l1_train": float(l1_train), "l1_test": float(l1_test), "palette_train": p_train, "palette_test": p_test,
+                     "wall_s": round(wall, 1), **kw}
+        print(f"[{name}] L1 {float(l1_train):.5f} / {float(l1_test):.5f}, off-palette {p_train['off_palette']:.5f} / "
+              f"{p_test['off_palette']:.5f} (train/test), {wall:.1f} s", file=sys.stderr, flush=True)
+    return res
 
 
 if __name__ == "__main__":
