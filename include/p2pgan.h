@@ -379,6 +379,28 @@ int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* pal
 int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,
                      float* image_out, int* dist_out, int* counts_out, long long* stats_out, void* stream);
 
+/* ---- differentiable augmentation (build-added, DESIGN.md "differentiable augmentation") --------------------------- */
+/* DiffAugment (Zhao et al., NeurIPS 2020) of dense f32 RGBA images [N][H][W][4], 16-byte aligned, any H, W >= 1 (H * W <= 2^28,
+ * N <= 65535).  color: f32 [N][3] = brightness offset b, saturation factor s, contrast factor k; geometry: int32 [N][4] = ty, tx,
+ * y0, x0 (any int32); both in device memory.  policy_bits: 1 colour | 2 translation | 4 cutout; a stage whose bit is clear does not
+ * read its table (color / geometry may then be NULL).  Per image, in this order:
+ *   colour       channels 0..2 of every pixel: u = x + b;  v = (u - mean_c u) s + mean_c u;  y = (v - m) k + m, where m, the mean of v
+ *                over the image's H W 3 values, is taken as mean_rgb(x) + b (equal in real arithmetic).  Alpha is untouched.
+ *   translation  out[r][c] = y[r - ty][c - tx] where that pixel exists, else `fill` in all four channels.
+ *   cutout       out[r][c] = fill for y0 <= r < y0 + ch and x0 <= c < x0 + cw (the box may hang over the border; ch, cw >= 0).
+ * Without the colour bit the result is a bit-exact copy / move / fill.  out must not be img.  workspace:
+ * p2p_diffaug_workspace_bytes(N, H, W) bytes, needed by the colour stage only (one partial sum per 1024 pixels; the sums are
+ * tree-shaped, in a fixed order, without float atomics, and an image's sum does not depend on N or on its place in the batch). */
+long long p2p_diffaug_workspace_bytes(int N, int H, int W);
+int p2p_diffaug_fwd(int N, int H, int W, const float* img, const float* color, const int* geometry, int ch, int cw,
+                    int policy_bits, float fill, float* out, float* workspace, void* stream);
+/* Its VJP with respect to img (the tables are not differentiable; img itself is not needed).  With g' = grad_out carried back to
+ * the source positions, 0 where the output was a fill, Gamma = sum of g' over the image's pixels and three colour channels and
+ * M = 3 H W:   dv = k g' + (1 - k) Gamma / M,   grad_img_c = s dv_c + (1 - s) / 3 sum_c' dv_c' (c < 3),   grad_img_3 = g'_3.
+ * Every element of grad_img is written.  `fill` is ignored (one argument list serves both calls); workspace as above. */
+int p2p_diffaug_bwd(int N, int H, int W, const float* grad_out, const float* color, const int* geometry, int ch, int cw,
+                    int policy_bits, float fill, float* grad_img, float* workspace, void* stream);
+
 /* ---- palette-index head (pix2pix_model.py:261-325) ------------------------------------------------------------ */
 
 /* z: logits view [N][H][W][C]; target: view holding the real palette index of every pixel (as a value of `dtype`).

@@ -86,6 +86,8 @@ SIGNATURES = {
     "p2p_soft_palette_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp],
     "p2p_palette_extract": [_i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "p2p_palette_snap": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "p2p_diffaug_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "p2p_diffaug_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "p2p_softmax_cce_argmax": [_i, _i, _i, _i, _i, _TP, _TP, _TP, _f, _f, _TP, _vp, _vp, _vp, _vp],
     "p2p_softmax_bwd": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _TP, _vp],
     "p2p_argmax_lastdim": [_vp, _ll, _i, _vp, _vp],
@@ -126,6 +128,7 @@ SPECIAL = {"p2p_last_error": ([], C.c_char_p),
            "p2p_wgemm_workspace_bytes": ([_i, _i, _i, _i, _i, _i], C.c_longlong),
            "p2p_rgbuv_hist_fwd3_workspace_bytes": ([_i], C.c_longlong),
            "p2p_soft_palette_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+           "p2p_diffaug_workspace_bytes": ([_i, _i, _i], C.c_longlong),
            "p2p_head_softmax_ok": ([_i, _i, _i, _i, _i, _i], C.c_int),
            "p2p_head_dgrad_ok": ([_i, _i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
            "p2p_head_softmax_workspace_bytes": ([_i, _i], C.c_longlong),

@@ -5,6 +5,7 @@
     Pix2PixHistogramModel(..., lambda_l1, lambda_histogram)
     Pix2PixIndexedModel(train_ds, test_ds, model_name, architecture_name, lambda_segmentation=0.5)
     Pix2PixPaletteModel(..., lambda_l1, lambda_palette, lambda_conformance=0.0, temperature=1e-3)      -- build-added
+    Pix2PixDiffAugmentModel(..., lambda_l1, policy="color,translation,cutout")                         -- build-added
 
 The constructor follows the reference's (pix2pix_model.py:12-36): create_generator() / create_discriminator() with the
 reference's builder signatures, `loss_object`, two Adam(0.0002, beta_1=0.5) optimizers, `checkpoint`,
@@ -30,6 +31,7 @@ Ragged global batches and ranks with an empty shard are handled.
 import torch
 
 from . import _lib as L
+from . import diffaugment as _diffaugment
 from . import histogram as _histogram  # noqa: F401  (module parity with the reference's `import histogram`)
 from . import palette as _palette
 from .configuration import IMG_SIZE, MAX_PALETTE_SIZE
@@ -400,6 +402,55 @@ class Pix2PixPaletteModel(Pix2PixAugmentedModel):
     def log_generator_loss(self, g_loss, step):
         super().log_generator_loss(g_loss[:3], step)
         self.summary_writer.scalar("generator/palette_loss", g_loss[3], step)
+
+
+class Pix2PixDiffAugmentModel(Pix2PixModel):
+    """Build-added (no counterpart in the reference): the RGBA model with differentiable augmentation in front of the
+    discriminator (diffaugment.py; DiffAugment, Zhao et al. 2020), for training sets of a few hundred pairs.  Where
+    Pix2PixAugmentedModel augments the dataset -- and so changes what the generator is asked to produce -- this class leaves the
+    batch alone and augments what the DISCRIMINATOR sees; the generator's gradient flows back through the augmentation.
+
+    train_step is the reference's step (pix2pix_model.py:62-89) written for tf.GradientTape.  ONE parameter table, drawn from
+    (seed, step) alone, serves the real and the fake pair, and the source image, which both pairs share, is augmented once: the two
+    pairs the discriminator compares differ only in the image under judgement.  The L1 term is taken on the un-augmented images.
+    `policy` is a comma-separated subset of diffaugment.POLICIES ("" trains as the plain tape step does).  Like every tape step it
+    runs on one GPU and is not replayed; generate() and the report_* evaluations are inherited: augmentation never touches inference."""
+
+    def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, policy="color,translation,cutout", **kw):
+        _diffaugment.policy_bits(policy)          # an unknown name fails here, not at the first step
+        super().__init__(train_ds, test_ds, model_name, architecture_name, lambda_l1, **kw)
+        self.policy = policy
+
+    def augmented_step(self, source_image, real_image, step, masks=None, apply=True):
+        """one step at the parameter table of `step`: (g_loss, d_loss, generator gradients, discriminator gradients), both
+        gradients taken at the pre-update weights.  masks: injected dropout keep-masks instead of the device's draw; apply=False
+        leaves the weights alone."""
+        from .tape import GradientTape
+        source_image, real_image = self._upload([source_image, real_image])
+        B = len(source_image)
+        p = _diffaugment.draw_parameters(B, self._img_size, self._img_size, self.policy, self._seed, int(step))
+        with GradientTape(persistent=True) as tape:
+            fake_image = self.generator(source_image, training=True, masks=masks)
+            source_aug = _diffaugment.diff_augment(source_image, p, self.policy, device=self.engine.device)
+            real_aug = _diffaugment.diff_augment(real_image, p, self.policy, device=self.engine.device)
+            fake_aug = _diffaugment.diff_augment(fake_image, p, self.policy, device=self.engine.device)
+            real_predicted = self.discriminator([real_aug, source_aug], training=True)
+            fake_predicted = self.discriminator([fake_aug, source_aug], training=True)
+            g_loss = self.generator_loss(fake_predicted, fake_image, real_image)
+            d_loss = self.discriminator_loss(real_predicted, fake_predicted)
+        generator_gradients = tape.gradient(g_loss[0], self.generator.trainable_variables)
+        discriminator_gradients = tape.gradient(d_loss[0], self.discriminator.trainable_variables)
+        if apply:
+            self.generator_optimizer.apply_gradients(zip(generator_gradients, self.generator.trainable_variables))
+            self.discriminator_optimizer.apply_gradients(zip(discriminator_gradients, self.discriminator.trainable_variables))
+        tape.release()
+        return tuple(x.detach() for x in g_loss), tuple(x.detach() for x in d_loss), generator_gradients, discriminator_gradients
+
+    def train_step(self, batch, step, update_steps):
+        source_image, real_image = batch
+        g_loss, d_loss, _, _ = self.augmented_step(source_image, real_image, step)
+        self._log(g_loss, d_loss, step, update_steps)
+        return g_loss, d_loss
 
 
 class Pix2PixIndexedModel(Pix2PixModel):
