@@ -227,6 +227,17 @@ int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C,
                      const p2p_tensor* draw, float* dgamma_part, float* dbeta_part,
                      float* ws, long long ws_bytes, int nsplit, void* stream);
 
+/* InstanceNorm block over a 1x1 map (H = W = 1; the generator's bottleneck at 64x64 inputs).  x - mean(x) is 0 over one pixel,
+ * so the output is act(drop(0 * gamma + beta)) whatever the convolution produced, d(raw) and dgamma are 0 and dbeta_part is
+ * d(yhat) = (g1 + g2) * slope * keep.  The forward form reads no convolution result and writes no statistics, the backward form
+ * reads neither and writes no d(raw); out, dbeta_part and dgamma_part (= 0) are bit-identical to p2p_norm_act_fwd /
+ * p2p_norm_act_bwd at H = W = 1 (mask, views and gradient sources as there).  C % 8 == 0 and 16-byte aligned pixels. */
+int p2p_norm_act_fwd_1x1(int dtype, int N, int C, const float* gamma, const float* beta, int act, float alpha,
+                         const unsigned char* mask, const p2p_tensor* out, void* stream);
+int p2p_norm_act_bwd_1x1(int dtype, int N, int C, const float* gamma, const float* beta, int act, float alpha,
+                         const unsigned char* mask, const p2p_gsrc* g1, const p2p_gsrc* g2, float* dgamma_part,
+                         float* dbeta_part, void* stream);
+
 /* Backward of a LeakyReLU that was fused into a conv epilogue (only its OUTPUT is stored):
  * draw = (g1 + g2) * (act_out > 0 ? 1 : alpha). */
 int p2p_act_bwd(int dtype, int N, int H, int W, int C, const p2p_tensor* act_out, const p2p_gsrc* g1,
@@ -456,6 +467,11 @@ int p2p_adam_flat(float* p, const float* g, float* m, float* v, long long n, int
 int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1, float beta2, void* stream);
 int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_t_dev,
                       float beta1, float beta2, float eps, float gscale, void* stream);
+/* p2p_adam_flat_dev that leaves the elements [ex_lo, ex_hi) of all four buffers alone (neither read nor written; any alignment)
+ * in ONE launch: a tensor whose gradient is identically 0 (and whose moments are 0) does not move under Adam.  Bit-identical to
+ * p2p_adam_flat_dev outside the range. */
+int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float* v, long long n, long long ex_lo, long long ex_hi,
+                           const float* lr_t_dev, float beta1, float beta2, float eps, float gscale, void* stream);
 int p2p_counter_add(long long* counter_dev, long long inc, void* stream);
 /* f32 gradient sum of a GradientTape (tape.py): a network's weight gradients over several calls, the two terms of a generator
  * call's d(source).  dst = src when `first` is set (the first contribution), dst += src otherwise; n floats, 16-byte aligned,

@@ -45,6 +45,8 @@ SIGNATURES = {
     "p2p_norm_act_fwd": [_i, _i, _i, _i, _i, _vp, _i, _i, _ll, _vp, _vp, _f, _i, _f, _vp, _TP, _vp, _vp, _vp, _ll, _i, _vp],
     "p2p_norm_act_fwd_tail": [_i, _i, _i, _i, _i, _vp, _i, _i, _ll, _vp, _vp, _f, _i, _f, _vp, _TP, _vp, _vp, _vp, _ll, _i, _TP, _i, _vp],
     "p2p_norm_act_bwd": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _GP, _GP, _TP, _vp, _vp, _vp, _ll, _i, _vp],
+    "p2p_norm_act_fwd_1x1": [_i, _i, _i, _vp, _vp, _i, _f, _vp, _TP, _vp],
+    "p2p_norm_act_bwd_1x1": [_i, _i, _i, _vp, _vp, _i, _f, _vp, _GP, _GP, _vp, _vp, _vp],
     "p2p_colsum": [_vp, _i, _i, _f, _vp, _vp],
     "p2p_colsum_batched": [_vp, _vp, _i, _i, _vp, _vp],
     "p2p_bce_logits": [_i, _i, _i, _i, _i, _TP, _f, _TP, _TP, _vp, _vp],
@@ -57,6 +59,7 @@ SIGNATURES = {
     "p2p_adam_flat": [_vp, _vp, _vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _vp],
     "p2p_adam_tick": [_vp, _vp, _f, _f, _f, _vp],
     "p2p_adam_flat_dev": [_vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _vp],
+    "p2p_adam_flat_dev_excl": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _f, _f, _f, _f, _vp],
     "p2p_counter_add": [_vp, _ll, _vp],
     "p2p_grad_accumulate": [_vp, _vp, _ll, _i, _vp],
     "p2p_dropout_mask_dev": [_vp, _ll, _ll, _vp, _ll, _ll, _vp],

@@ -1284,6 +1284,101 @@ extern "C" int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C, const voi
     return p2p_check_launch("p2p_norm_act_bwd");
 }
 
+// ---------------------------------------------------------------------------------------------------
+// InstanceNorm over a 1x1 map (the U-Net bottleneck at 64x64 inputs).  The mean of one pixel is the pixel, so x - mean is +0
+// whatever the convolution produced: the output is act(drop(0 * gamma + beta)), d(raw) is 0, dgamma is 0 and only
+// dbeta = d(yhat) is live.  These two kernels are norm_act_fwd_small / norm_act_bwd_small at HW = 1 (one lane per (image,
+// VN-channel vector), the same expressions in the same order: bit-identical results) without the loads of x and the
+// statistics and without the store of d(raw).  (0 * gamma keeps the sign of gamma, as (x - mean) * rstd * gamma does.)
+template <typename T>
+__global__ __launch_bounds__(256) void norm_act_fwd_1x1_kernel(int C, long long items, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, int act, float alpha,
+                                                               const unsigned char* __restrict__ mask, TView out) {
+    constexpr int VN = VecOf<T>::N;
+    const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (item >= items) return;
+    const int cvn = C / VN;
+    const int n = (int)(item / cvn), c = (int)(item - (long long)n * cvn) * VN;
+    float keep[VN], y[VN];
+    if (mask) mask_vload8(mask + (long long)n * C + c, keep, VN);
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        float v = 0.f * gamma[c + k] + beta[c + k];
+        if (mask) v *= keep[k];
+        if (act == P2P_ACT_LEAKY) v = v > 0.f ? v : alpha * v;
+        else if (act == P2P_ACT_RELU) v = v > 0.f ? v : 0.f;
+        y[k] = v;
+    }
+    vstore<T>((T*)out.ptr + out.off(n, 0, 0) + c, y);
+}
+
+template <typename T, int SLABS>
+__global__ __launch_bounds__(256) void norm_act_bwd_1x1_kernel(int C, long long items, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, int act, float alpha,
+                                                               const unsigned char* __restrict__ mask, GSrc g1, GSrc g2,
+                                                               float* __restrict__ dgamma_part, float* __restrict__ dbeta_part) {
+    constexpr int VN = VecOf<T>::N;
+    const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (item >= items) return;
+    const int cvn = C / VN;
+    const int n = (int)(item / cvn), c = (int)(item - (long long)n * cvn) * VN;
+    float a1[VN], a2[VN], keep[VN];
+    gsrc_vload<T, SLABS>(g1, n, c, a1);
+    gsrc_vload<T, SLABS>(g2, n, c, a2);
+    if (mask) mask_vload8(mask + (long long)n * C + c, keep, VN);
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        float a = 0.f * gamma[c + k] + beta[c + k];
+        const float kp = mask ? keep[k] : 1.f;
+        a *= kp;
+        float slope = 1.f;
+        if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
+        else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
+        const float d = (a1[k] + a2[k]) * slope * kp;
+        dbeta_part[(long long)n * C + c + k] = 0.f + d;     // (the sum over one pixel starts from +0)
+        dgamma_part[(long long)n * C + c + k] = 0.f;
+    }
+}
+
+static bool gsrc_vec_ok(const p2p_gsrc* g, int vn) {
+    if (!g || !g->ptr || g->kind != 1) return true;     // f32 slabs are read element-wise unless they are aligned
+    return g->ld % vn == 0 && g->coff % vn == 0 && ((uintptr_t)g->ptr % 16) == 0;
+}
+
+extern "C" int p2p_norm_act_fwd_1x1(int dtype, int N, int C, const float* gamma, const float* beta, int act, float alpha,
+                                    const unsigned char* mask, const p2p_tensor* out, void* stream) {
+    P2P_REQUIRE(N > 0 && C > 0, "p2p_norm_act_fwd_1x1: bad shape");
+    P2P_REQUIRE(gamma && beta && out && out->ptr, "p2p_norm_act_fwd_1x1: null pointer");
+    const int vn = dtype == P2P_BF16 ? 8 : 4;
+    P2P_REQUIRE(C % 8 == 0 && out->ld % vn == 0 && ((uintptr_t)out->ptr % 16) == 0,
+                "p2p_norm_act_fwd_1x1: pixels must be whole 16-byte vectors (C %% 8 == 0, aligned view)");
+    const long long items = (long long)N * (C / vn);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_1x1_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>(C, items, gamma, beta, act, alpha, mask,
+                                                                                                 make_view(out))));
+    return p2p_check_launch("p2p_norm_act_fwd_1x1");
+}
+
+extern "C" int p2p_norm_act_bwd_1x1(int dtype, int N, int C, const float* gamma, const float* beta, int act, float alpha,
+                                    const unsigned char* mask, const p2p_gsrc* g1, const p2p_gsrc* g2, float* dgamma_part,
+                                    float* dbeta_part, void* stream) {
+    P2P_REQUIRE(N > 0 && C > 0, "p2p_norm_act_bwd_1x1: bad shape");
+    P2P_REQUIRE(gamma && beta && g1 && dgamma_part && dbeta_part, "p2p_norm_act_bwd_1x1: null pointer");
+    const int vn = dtype == P2P_BF16 ? 8 : 4;
+    P2P_REQUIRE(C % 8 == 0 && gsrc_vec_ok(g1, vn) && gsrc_vec_ok(g2, vn),
+                "p2p_norm_act_bwd_1x1: pixels must be whole 16-byte vectors (C %% 8 == 0, aligned gradient sources)");
+    const bool g_slabs = g1->kind == 2 || (g2 && g2->kind == 2);
+    const long long items = (long long)N * (C / vn);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+#define NB_1X1(S_) norm_act_bwd_1x1_kernel<T, S_><<<grid, 256, 0, st>>>(C, items, gamma, beta, act, alpha, mask, make_gsrc(g1), make_gsrc(g2), \
+                                                                       dgamma_part, dbeta_part)
+    if (g_slabs) { P2P_DISPATCH_DTYPE(dtype, NB_1X1(4)); }
+    else { P2P_DISPATCH_DTYPE(dtype, NB_1X1(0)); }
+#undef NB_1X1
+    return p2p_check_launch("p2p_norm_act_bwd_1x1");
+}
+
 extern "C" int p2p_colsum(const float* part, int rows, int cols, float scale, float* out, void* stream) {
     P2P_REQUIRE(part && out && rows > 0 && cols > 0, "p2p_colsum: bad args");
     colsum_kernel<<<dim3((cols + 255) / 256), 256, 0, (hipStream_t)stream>>>(part, rows, cols, scale, out);

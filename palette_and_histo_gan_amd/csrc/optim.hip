@@ -40,6 +40,19 @@ __global__ void adam_tick_kernel(int* __restrict__ t, float* __restrict__ lr_t, 
     lr_t[0] = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)tt)) / (1.0 - pow((double)b1, (double)tt)));
 }
 
+// One element of the Keras Adam step with its roundings spelled out: m' = fma(1 - b1, g, b1 * m), v' = fma(b2, v, ((1 - b2) * g) * g).
+// That is what the compiler's contraction made of the vector loop of adam_flat_dev_kernel; left to the compiler, a scalar copy of
+// the same expressions (a tail, a vector cut by an excluded range) came out with other fusions and other last bits.  Every path
+// of adam_flat_dev_kernel and adam_flat_dev_excl_kernel goes through here: they agree bit for bit by construction.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
+                                            float gscale) {
+#pragma clang fp contract(off)
+    const float gg = g * gscale;
+    m = __builtin_fmaf(1.f - b1, gg, b1 * m);
+    v = __builtin_fmaf(b2, v, ((1.f - b2) * gg) * gg);
+    p = p - lr_t * m / (sqrtf(v) + eps);
+}
+
 __global__ void adam_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                      float* __restrict__ v, long long n, const float* __restrict__ lr_t_dev, float b1,
                                      float b2, float eps, float gscale) {
@@ -50,20 +63,15 @@ __global__ void adam_flat_dev_kernel(float* __restrict__ p, const float* __restr
         f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float gg = gi[k] * gscale;
-            mi[k] = b1 * mi[k] + (1.f - b1) * gg;
-            vi[k] = b2 * vi[k] + (1.f - b2) * gg * gg;
-            pi[k] = pi[k] - lr_t * mi[k] / (sqrtf(vi[k]) + eps);
+            float pk = pi[k], mk = mi[k], vk = vi[k];
+            adam_update(pk, gi[k], mk, vk, lr_t, b1, b2, eps, gscale);
+            pi[k] = pk; mi[k] = mk; vi[k] = vk;
         }
         *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
     }
     // tail (n is padded to a multiple of 4 by the host layout, kept for safety)
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long j = n / 4 * 4; j < n; ++j) {
-            float gg = g[j] * gscale;
-            float mj = b1 * m[j] + (1.f - b1) * gg, vj = b2 * v[j] + (1.f - b2) * gg * gg;
-            m[j] = mj; v[j] = vj; p[j] = p[j] - lr_t * mj / (sqrtf(vj) + eps);
-        }
+        for (long long j = n / 4 * 4; j < n; ++j) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
 }
 
 extern "C" int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1, float beta2, void* stream) {
@@ -82,6 +90,56 @@ extern "C" int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, l
     if (blocks < 1) blocks = 1;
     adam_flat_dev_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps, gscale);
     return p2p_check_launch("p2p_adam_flat_dev");
+}
+
+// adam_flat_dev_kernel with a hole: elements [ex_lo, ex_hi) are neither read nor written.  The 16-byte vectors that lie wholly
+// inside the hole are taken out of the index space (every lane keeps a whole share of live vectors); a vector that straddles an
+// end of the hole is updated element by element.  The arithmetic is adam_update's, as in adam_flat_dev_kernel: bit-identical
+// outside the hole.
+__global__ void adam_flat_dev_excl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, long long n, long long ex_lo, long long ex_hi,
+                                          const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale) {
+    const float lr_t = lr_t_dev[0];
+    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
+    const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
+    const long long live = n / 4 - hole;
+    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; q < live; q += stride) {
+        const long long i = (q < hv_lo ? q : q + hole) * 4;
+        if (i + 4 <= ex_lo || i >= ex_hi) {
+            f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pi[k], mk = mi[k], vk = vi[k];
+                adam_update(pk, gi[k], mk, vk, lr_t, b1, b2, eps, gscale);
+                pi[k] = pk; mi[k] = mk; vi[k] = vk;
+            }
+            *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
+        } else {
+            for (long long j = i; j < i + 4; ++j)
+                if (j < ex_lo || j >= ex_hi) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = n / 4 * 4; j < n; ++j)
+            if (j < ex_lo || j >= ex_hi) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+}
+
+extern "C" int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float* v, long long n, long long ex_lo, long long ex_hi,
+                                      const float* lr_t_dev, float beta1, float beta2, float eps, float gscale, void* stream) {
+    P2P_REQUIRE(p && g && m && v && n > 0 && lr_t_dev, "p2p_adam_flat_dev_excl: bad args");
+    P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_adam_flat_dev_excl: the excluded range must lie inside [0, n)");
+    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+                "p2p_adam_flat_dev_excl: buffers must be 16-byte aligned");
+    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
+    const long long live = n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
+    long long blocks = (live + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    adam_flat_dev_excl_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1,
+                                                                                       beta2, eps, gscale);
+    return p2p_check_launch("p2p_adam_flat_dev_excl");
 }
 
 __global__ void counter_add_kernel(long long* c, long long inc) { c[0] += inc; }

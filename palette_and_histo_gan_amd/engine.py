@@ -543,6 +543,23 @@ class Pix2PixEngine:
         # (tests/test_hist_indexed_gpu.py calls them directly); the engine has one path
         self.hist_fwd3 = self.hist_bwd3 = self.hist_points = 1
         self.split_prep = int(os.environ.get("P2P_SPLIT_PREP", "1"))    # weight copies of the early-Adam part refreshed right behind it
+        # The encoder block whose output map is 1x1 under InstanceNorm (the sixth at 64x64; none from 128x128 on): over one pixel
+        # x - mean(x) is exactly 0, so its output is act(beta) whatever its convolution computes, d(raw) is exactly 0, and with it
+        # its kernel's and gamma's gradients and the data gradient it hands to the block above; Adam never moves the kernel
+        # (DESIGN.md section 4).  The fused train steps leave that work out: 0 = issue everything; 1 = no forward / data-gradient
+        # / weight-gradient GEMM of the block and its kernel out of the in-step weight-copy launch, with the entry points and the
+        # launch count per entry point the step has always had (the normalisation runs on a zero "convolution result", Adam
+        # still passes over the kernel and leaves it as it is); 2 = also the 1x1 normalisation kernels that read no convolution
+        # result (p2p_norm_act_fwd_1x1 / _bwd_1x1) and Adam with a hole (p2p_adam_flat_dev_excl).  Bit-identical results at
+        # every level (tests/test_dead_bottleneck_gpu.py).
+        self.elide_dead_bottleneck = int(os.environ.get("P2P_ELIDE_DEAD", "1"))
+        self._dead = next((i for i in range(2, len(DOWN_FILTERS) + 1) if img_size // 2 ** i == 1), None)
+        self._frozen = None             # element range of the dead block's kernel in the generator's flat buffers
+        if self._dead is not None:
+            o = self.G.offsets[f"down{self._dead}.kernel"]
+            self._frozen = (o, o + int(np.prod(self.G.shapes[f"down{self._dead}.kernel"])))
+        self._frozen_ok = None          # its gradient and Adam moments are all 0 (None: not looked at since the last outside write)
+        self._elide = 0                 # the level in force: non-zero only inside a fused train step
         self.refresh_weight_copies()
 
     def _slot_property(slot):
@@ -600,18 +617,24 @@ class Pix2PixEngine:
                     lw.wd = torch.zeros(16 * cg * cd, dtype=tdt, device=dev)
                 self.W[(sid, name)] = lw
 
-    def _prep_tasks(self, part="all"):
+    def _prep_tasks(self, part="all", live=False):
         """Device table of p2p_prep_task descriptors (one per weight copy set); the pointers are stable for the life
         of the engine, so it is built once.  part = "head": the generator layers whose parameters lie in front of the last
         gradient bucket (what _adam_head updates early), "rest": the others, "all": every layer, "G" / "D": one network's
-        layers (the per-network optimizer step, apply_adam_store)."""
+        layers (the per-network optimizer step, apply_adam_store).  live: without the dead bottleneck's kernel (its master does
+        not move inside a fused step; every outside writer refreshes the complete table)."""
+        want = part
+        if live:
+            part = (part, "live")           # (the cache key from here on)
         if self._prep_table.get(part) is not None:
             return self._prep_table[part]
         head_end = self.G.buckets[-1][0] if len(self.G.buckets) >= 2 else 0
         specs = []
         for (sid, name), lw in self.W.items():
             in_head = sid == "G" and self.G.offsets[name + ".kernel"] + 16 * lw.cg * lw.cd <= head_end
-            if (part == "head" and not in_head) or (part == "rest" and in_head) or (part in ("G", "D") and sid != part):
+            if (want == "head" and not in_head) or (want == "rest" and in_head) or (want in ("G", "D") and sid != want):
+                continue
+            if live and (sid, name) == ("G", f"down{self._dead}"):
                 continue
             master = self._store(sid).p(name + ".kernel")
             if lw.wt is not None or lw.wn is not None:
@@ -694,10 +717,16 @@ class Pix2PixEngine:
         L.call("p2p_adam_prep_batched", self.dtype, n_elems, _p(raw), ntasks, total, _p(store.params), _p(store.grads), _p(store.m),
                _p(store.v), _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, _stream())
 
-    def refresh_weight_copies(self, part="all"):
-        """Re-derives the per-layer weight copies from the f32 masters; runs after every Adam step (one launch per part)."""
+    def refresh_weight_copies(self, part="all", outside=True):
+        """Re-derives the per-layer weight copies from the f32 masters; runs after every Adam step (one launch per part).
+        Everything that writes the masters from outside a train step (construction, set_params / set_weights, loading weights or a
+        checkpoint) ends here with outside=True: every copy is refreshed, the dead bottleneck's included, and the next fused step
+        looks at that kernel's Adam state again (_elision).  Inside a fused step that elides the block its copies are left alone.
+        Code that writes G.params / G.m / G.v / G.grads directly must end here too: the engine cannot see such a write."""
         self._copies_version += 1
-        raw, ntasks, total = self._prep_tasks(part)
+        if outside:
+            self._frozen_ok = None
+        raw, ntasks, total = self._prep_tasks(part, live=bool(self._elide))
         if ntasks:
             L.call("p2p_weight_prep_batched", self.dtype, _p(raw), ntasks, total, _stream())
 
@@ -708,6 +737,42 @@ class Pix2PixEngine:
     def _wd(self, sid, name):
         lw = self.W[(sid, name)]
         return _p(lw.wd) if lw.wd is not None else self._store(sid).p(name + ".kernel")
+
+    def _elision(self):
+        """the level of elide_dead_bottleneck a fused train step may run at now: 0 where no block normalises a 1x1 map, in the
+        f32 parity mode, on the direct cross-check path and with the fused Adam (they keep every launch), and unless the dead
+        kernel's gradient and Adam moments are all 0 -- Adam then leaves the kernel alone bit for bit.  (A checkpoint of a
+        128x128 run has the same shapes and live moments there.)  Looked at once after every outside write of the state."""
+        lvl = int(self.elide_dead_bottleneck)
+        if not lvl or self._dead is None or self.batch_invariant or not self.use_mfma or self.fuse_adam:
+            return 0
+        if self._frozen_ok is None:
+            # (three reductions and a host synchronisation, once per outside refresh.  Off a GPU -- the launch census of
+            # tests/step_launches.py runs this engine on device "meta", where no value can be read -- the state counts as fresh)
+            lo, hi = self._frozen
+            self._frozen_ok = self.device.type != "cuda" or not any(
+                bool(torch.count_nonzero(t[lo:hi])) for t in (self.G.grads, self.G.m, self.G.v))
+        return lvl if self._frozen_ok else 0
+
+    def _zero_raw(self, P, N, c):
+        """a dense zero [N][c] "convolution result" of the dead bottleneck: any finite value normalises to the same output"""
+        z = P.get("zraw")
+        if z is None:
+            z = P["zraw"] = DenseBuf(N, 1, 1, c, self.tdt, self.device)
+            z.t.zero_()
+        return z
+
+    def _adam_range(self, store, lo, hi):
+        """Keras Adam on the elements [lo, hi) of a store's flat buffers.  At level 2 of elide_dead_bottleneck the dead kernel is a
+        hole in the launch (g = m = v = 0 there: the plain launch leaves it bit for bit as it is, and reads and writes it)."""
+        ex = self._frozen if (self._elide >= 2 and store is self.G) else None
+        if ex is not None and lo <= ex[0] and ex[1] <= hi:
+            L.call("p2p_adam_flat_dev_excl", _p(store.params, lo), _p(store.grads, lo), _p(store.m, lo), _p(store.v, lo), hi - lo,
+                   ex[0] - lo, ex[1] - lo, _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+            return
+        assert ex is None or ex[1] <= lo or hi <= ex[0], "the dead kernel straddles an Adam range"
+        L.call("p2p_adam_flat_dev", _p(store.params, lo), _p(store.grads, lo), _p(store.m, lo), _p(store.v, lo), hi - lo,
+               _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
 
     def set_params(self, g_values=None, d_values=None):
         if g_values is not None:
@@ -968,27 +1033,32 @@ class Pix2PixEngine:
                                 and UP_FILTERS[5] % 8 == 0 and S * S > 16)
         return P[key]
 
-    def _wgrad(self, P, sid, name, N, lh, hi, lo, stride=2, dbias=None):
+    def _wgrad(self, P, sid, name, N, lh, hi, lo, stride=2, dbias=None, dead=False):
         """dW (and dbias) of one layer, issued on the side stream: its inputs were produced on the main stream
-        before this call (fork), its outputs are only read by Adam (join in _finish_step)."""
+        before this call (fork), its outputs are only read by Adam (join in _finish_step).  dead: the gradient is identically 0
+        and stays as allocated (elide_dead_bottleneck) -- only what its completion triggers is issued, if anything."""
+        dp = self._dp
+        nb, b = len(self.G.buckets), self.G.bucket_of[name] if sid == "G" else None
+        closes = sid == "G" and self.G.bucket_last_layer[b] == name         # the last kernel gradient of its bucket
+        # single GPU: every weight gradient in front of the last bucket has been issued -- Adam may start on that part of the
+        # flat buffer while this stream is still busy with the last layers (see _finish_step)
+        head_done = dp is None and closes and self.side.enabled and nb >= 2 and b == nb - 2
+        # data parallel: every kernel gradient of this bucket has been issued on this stream -- all-reduce it now, concurrently
+        # with the rest of the backward pass (SURVEY.md section 5).  The LAST bucket completes with the last weight gradient
+        # of the step and sits right in front of the small-tensor tail: both leave together in _reduce_tail (one collective
+        # less on the exposed end of the step)
+        reduce_now = dp is not None and closes and b != nb - 1
+        if dead and not (head_done or reduce_now):
+            return
         self.side.fork()
         with self.side.run():
-            self._wgrad_impl(P, sid, name, N, lh, hi, lo, stride, dbias)
-            dp = self._dp
-            if dp is None and sid == "G" and self.side.enabled and len(self.G.buckets) >= 2 \
-                    and self.G.bucket_last_layer[len(self.G.buckets) - 2] == name:
-                # every weight gradient in front of the last bucket has been issued: Adam may start on that part of the
-                # flat buffer while this stream is still busy with the last layers (see _finish_step)
+            if not dead:
+                self._wgrad_impl(P, sid, name, N, lh, hi, lo, stride, dbias)
+            if head_done:
                 self._adam_head_ev = _record_event()
-            if dp is not None and sid == "G":
-                b = self.G.bucket_of[name]
-                if self.G.bucket_last_layer[b] == name and b != len(self.G.buckets) - 1:
-                    # every kernel gradient of this bucket has been issued on this stream: all-reduce it now,
-                    # concurrently with the rest of the backward pass (SURVEY.md section 5).  The LAST bucket completes
-                    # with the last weight gradient of the step and sits right in front of the small-tensor tail: both
-                    # leave together in _reduce_tail (one collective less on the exposed end of the step)
-                    lo_e, hi_e = self.G.buckets[b]
-                    dp.allreduce_async(self.G.grads[lo_e:hi_e])
+            if reduce_now:
+                lo_e, hi_e = self.G.buckets[b]
+                dp.allreduce_async(self.G.grads[lo_e:hi_e])
 
     def _wgrad_impl(self, P, sid, name, N, lh, hi, lo, stride=2, dbias=None):
         lw = self.W[(sid, name)]
@@ -1065,10 +1135,12 @@ class Pix2PixEngine:
         slabs = rk[2] if len(rk) == 3 else P["slabs"]
         return L.GSrc(slabs.data_ptr(), 2, rk[1], buf.n * buf.h * buf.w * buf.c, buf.c, coff)
 
-    def _norm_bwd(self, P, name, N, res, c, raw_buf, stats, act, mask, g1, g2, draw_view):
-        """(every caller forks the layer's weight gradient right behind this call: the fork rides on the kernel's completion)"""
+    def _norm_bwd(self, P, name, N, res, c, raw_buf, stats, act, mask, g1, g2, draw_view, fork_follows=True):
+        """(every caller but the elided bottleneck forks the layer's weight gradient right behind this call: the fork rides on the
+        kernel's completion)"""
         ob, og = P["part_off"][name]
-        self.side.prefork()
+        if fork_follows:
+            self.side.prefork()
         L.call("p2p_norm_act_bwd", self.dtype, N, res, res, c, raw_buf.ptr(), _p(stats), self.G.p(name + ".gamma"),
                self.G.p(name + ".beta"), act, LEAKY_ALPHA, _p(mask) if mask is not None else NULL, C.byref(g1),
                C.byref(g2) if g2 is not None else None, C.byref(draw_view), _p(P["part"], og), _p(P["part"], ob),
@@ -1117,7 +1189,7 @@ class Pix2PixEngine:
         return (kind, B, self.side.enabled, self.side.stop_event_forks, self.side_hist.enabled, self.fuse_adam, self.use_head_fused, self.hist_fwd3, self.hist_bwd3,
                 self.hist_points, self.fuse_act_bwd, self.split_prep, self.full_pixels, self.use_conv_fewout, self.use_conv_strip, self.use_conv_fewin,
                 self.use_mfma, bool(self.batch_invariant), bool(self.wgemm_pipe), int(self.splitk_target), int(self.wgemm_want), int(self.wgemm_want_pipe),
-                int(st.cuda_stream), int(st.stream_id),
+                int(st.cuda_stream), int(st.stream_id), int(self._elide),
                 None if dp is None else id(dp)) + extra
 
     def _bind_batch(self, src_t, real_t):
@@ -1232,6 +1304,13 @@ class Pix2PixEngine:
             out_view = P["a6"].view() if i == 6 else c[6 - i].view(coff=UP_FILTERS[5 - i])
             if i == 1:      # no norm (networks.py:58): LeakyReLU fused in the conv epilogue
                 self._conv(P, L.OP_G, "G", "down1", B, res, src_view, out_view, act=L.ACT_LEAKY, tmp=P["rd"].get(1))
+            elif self._elide and i == self._dead:       # act(beta): no convolution (elide_dead_bottleneck)
+                if self._elide >= 2:
+                    L.call("p2p_norm_act_fwd_1x1", self.dtype, B, f, self.G.p(f"down{i}.gamma"), self.G.p(f"down{i}.beta"),
+                           L.ACT_LEAKY, LEAKY_ALPHA, NULL, C.byref(out_view), _stream())
+                else:
+                    self._norm_fwd(P, B, res, f, self._zero_raw(P, B, f), (1, 1), self.G.p(f"down{i}.gamma"),
+                                   self.G.p(f"down{i}.beta"), L.ACT_LEAKY, None, out_view, P["sd"][i])
             elif self._fused_block(P, L.OP_G, f"down{i}", B, res, src_view, P["rd"][i], L.ACT_LEAKY, out_view, P["sd"][i]):
                 pass
             else:
@@ -1314,22 +1393,26 @@ class Pix2PixEngine:
         self._dp = dp
         self._batch_offset = int(batch_offset)
         src_t, real_t = self._to_device(source, ic, B), self._to_device(real, ic, B)
-        key = self._replay_key("rgba", B, masks, dp, apply_update, float(lambda_l1),
-                               None if lambda_hist is None else float(lambda_hist), Bg, int(batch_offset))
-        if key in self._replays:
-            return self._replay(key, P, src_t, real_t, hist=lambda_hist is not None)
-        recording = self._begin_record(key)
-        if recording and dp is not None:
-            dp = self._dp = _RecDP(dp)
+        self._elide = self._elision()
         try:
-            out = self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, dp)
-        except BaseException:
+            key = self._replay_key("rgba", B, masks, dp, apply_update, float(lambda_l1),
+                                   None if lambda_hist is None else float(lambda_hist), Bg, int(batch_offset))
+            if key in self._replays:
+                return self._replay(key, P, src_t, real_t, hist=lambda_hist is not None)
+            recording = self._begin_record(key)
+            if recording and dp is not None:
+                dp = self._dp = _RecDP(dp)
+            try:
+                out = self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, dp)
+            except BaseException:
+                if recording:
+                    self._end_record(key, False)
+                raise
             if recording:
-                self._end_record(key, False)
-            raise
-        if recording:
-            self._end_record(key, True)
-        return out
+                self._end_record(key, True)
+            return out
+        finally:
+            self._elide = 0         # every other path (hooked steps, tapes, generate) issues the whole network
 
     def _train_step_rgba_body(self, P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, dp):
         S, ic = self.S, self.in_ch
@@ -1488,6 +1571,20 @@ class Pix2PixEngine:
             else:
                 g1 = self._gs(P, gc[6 - i], rk_gc[6 - i], UP_FILTERS[5 - i])     # skip-connection slice
                 g2 = g_from_down
+            if self._elide and i == self._dead:
+                # only dbeta is live: d(raw) is exactly 0, so there is no weight gradient to compute (its range of the flat
+                # gradient buffer has been 0 since allocation) and the block above receives its skip gradient alone
+                if self._elide >= 2:
+                    ob, og = P["part_off"][f"down{i}"]
+                    L.call("p2p_norm_act_bwd_1x1", self.dtype, B, f, self.G.p(f"down{i}.gamma"), self.G.p(f"down{i}.beta"),
+                           L.ACT_LEAKY, LEAKY_ALPHA, NULL, C.byref(g1), C.byref(g2) if g2 is not None else None,
+                           _p(P["part"], og), _p(P["part"], ob), _stream())
+                else:
+                    self._norm_bwd(P, f"down{i}", B, res, f, self._zero_raw(P, B, f), P["sd"][i], L.ACT_LEAKY, None, g1, g2,
+                                   P["dd"][i].view(), fork_follows=False)
+                self._wgrad(P, "G", f"down{i}", B, res, None, None, dead=True)
+                g_from_down = None
+                continue
             if i > 1:
                 self._norm_bwd(P, f"down{i}", B, res, f, P["rd"][i], P["sd"][i], L.ACT_LEAKY, None, g1, g2,
                                P["dd"][i].view())
@@ -1579,13 +1676,12 @@ class Pix2PixEngine:
             self._adam_prep("G_head")          # update + operand copies in one pass over the 26 M head parameters
             self._head_prepped = True
             return n
-        L.call("p2p_adam_flat_dev", _p(self.G.params), _p(self.G.grads), _p(self.G.m), _p(self.G.v), n,
-               _p(self.G.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+        self._adam_range(self.G, 0, n)
         if self.split_prep:
             # their weight copies too: the data-gradient kernels that read them are done (same stream), the other stream's
             # last weight gradients do not read weight copies -- a memory-bound launch beside MFMA-bound ones instead of
             # alone at the step boundary
-            self.refresh_weight_copies("head")
+            self.refresh_weight_copies("head", outside=False)
             self._head_prepped = True
         return n
 
@@ -1618,13 +1714,11 @@ class Pix2PixEngine:
             store.t += 1
             if not ticked:
                 L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
-            off = g_from if store is self.G else 0
-            L.call("p2p_adam_flat_dev", _p(store.params, off), _p(store.grads, off), _p(store.m, off), _p(store.v, off),
-                   store.numel - off, _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+            self._adam_range(store, g_from if store is self.G else 0, store.numel)
         if not ticked:
             L.call("p2p_counter_add", _p(self.mask_counter_dev), 1, _stream())
         head_done, self._head_prepped = self._head_prepped and g_from > 0, False
-        self.refresh_weight_copies("rest" if head_done else "all")
+        self.refresh_weight_copies("rest" if head_done else "all", outside=False)
 
     def _histogram_loss(self, P, B, Bg, lambda_hist, hist_allreduce):
         """Pix2PixHistogramModel.generator_loss (pix2pix_model.py:242-250): Hellinger(rgbuv_hist(real), rgbuv_hist(fake)).
@@ -1719,21 +1813,25 @@ class Pix2PixEngine:
         self._batch_offset = int(batch_offset)
         src_t = self._to_device(source_idx, 1, B, is_int=True)
         real_t = self._to_device(real_idx, 1, B, is_int=True)
-        key = self._replay_key("indexed", B, masks, dp, apply_update, float(lambda_segmentation), Bg, int(batch_offset))
-        if key in self._replays:
-            return self._replay(key, P, src_t, real_t)
-        recording = self._begin_record(key)
-        if recording and dp is not None:
-            self._dp = _RecDP(dp)
+        self._elide = self._elision()
         try:
-            out = self._train_step_indexed_body(P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update)
-        except BaseException:
+            key = self._replay_key("indexed", B, masks, dp, apply_update, float(lambda_segmentation), Bg, int(batch_offset))
+            if key in self._replays:
+                return self._replay(key, P, src_t, real_t)
+            recording = self._begin_record(key)
+            if recording and dp is not None:
+                self._dp = _RecDP(dp)
+            try:
+                out = self._train_step_indexed_body(P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update)
+            except BaseException:
+                if recording:
+                    self._end_record(key, False)
+                raise
             if recording:
-                self._end_record(key, False)
-            raise
-        if recording:
-            self._end_record(key, True)
-        return out
+                self._end_record(key, True)
+            return out
+        finally:
+            self._elide = 0
 
     def _pack_indexed(self, P, B, src_t, real_t):
         S = self.S
@@ -1910,7 +2008,7 @@ class Pix2PixEngine:
         for t, c in snap:
             t.copy_(c)
         self.G.t, self.D.t = t_host
-        self.refresh_weight_copies()
+        self.refresh_weight_copies(outside=False)        # (the state the warm-up step started from: no second look under capture)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):

@@ -118,6 +118,14 @@ def call_work(name, args, dtype):
         t = n * h * w * c
         by = t * esz + _gsrc_bytes(args[12], t, esz) + (_gsrc_bytes(args[13], t, esz) if args[13] is not None else 0) + t * esz
         return {"flops": 0.0, "mfma": None, "bytes": by}
+    if name == "p2p_norm_act_fwd_1x1":          # act(beta) out; no convolution result in
+        _, n, c = _ints(args, 3)
+        return {"flops": 0.0, "mfma": None, "bytes": float(n * c * esz)}
+    if name == "p2p_norm_act_bwd_1x1":          # the gradient sources in, the dbeta / dgamma partials out
+        _, n, c = _ints(args, 3)
+        t = n * c
+        return {"flops": 0.0, "mfma": None,
+                "bytes": _gsrc_bytes(args[8], t, esz) + (_gsrc_bytes(args[9], t, esz) if args[9] is not None else 0) + 2 * 4.0 * t}
     if name == "p2p_act_bwd":
         _, n, h, w, c = _ints(args, 5)
         t = n * h * w * c
@@ -166,6 +174,8 @@ def call_work(name, args, dtype):
         return {"flops": 0.0, "mfma": None, "bytes": n * h * w * (2.0 * c * esz + 2 * 8 * esz)}
     if name == "p2p_adam_flat_dev":
         return {"flops": 0.0, "mfma": None, "bytes": 7 * 4.0 * int(args[4])}        # g, m, v, p in; m, v, p out
+    if name == "p2p_adam_flat_dev_excl":      # the same streams without the excluded range
+        return {"flops": 0.0, "mfma": None, "bytes": 7 * 4.0 * (int(args[4]) - (int(args[6]) - int(args[5])))}
     if name == "p2p_adam_prep_batched":       # g, m, v, theta in; m, v, theta out; two operand copies out
         return {"flops": 0.0, "mfma": None, "bytes": (7 * 4.0 + 2 * esz) * int(args[1])}
     if name == "p2p_pack_pair":
