@@ -390,6 +390,25 @@ int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* pal
 int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,
                      float* image_out, int* dist_out, int* counts_out, long long* stats_out, void* stream);
 
+/* Differentiable palette projection (DESIGN.md "palette projection"): every pixel replaced by a colour of its image's palette.
+ * img, palette, sizes, K, tau and w_pk as for the soft histogram; n = clamp(sizes[n], 0, K); out: dense f32 [N][H][W][4], 16-byte
+ * aligned, every pixel written.
+ *   hard = 0:  out_p = 2 sum_k w_pk c_k - 1 in all four channels, the sum taken as c_r + sum_k w_pk (c_k - c_r) about the pixel's
+ *              nearest slot r (a min pass, then one exponential per pair);
+ *   hard = 1:  out_p = palette[argmin_k D_pk] / 127.5f - 1.0f by the integer rule of p2p_palette_snap (same device code): the bits
+ *              of its image_out.  tau is checked and otherwise unused.
+ *   n = 0:     out = img bit for bit.
+ * Purely per pixel: no workspace, no atomics, no cross-lane reduction; a pixel's bits depend on neither N nor its image's place. */
+int p2p_palette_project_fwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau, int hard,
+                            float* out, void* stream);
+/* The VJP of the SOFT projection at img for an upstream gradient g [N][H][W][4] (whichever forward ran: with hard = 1 it is the
+ * surrogate gradient of the snap):   dimg_p = (2 / tau) Cov_w(c) g_p,   Cov_w(c) = sum_k w_pk c_k c_k^T - (sum_k w_pk c_k)(sum_k w_pk c_k)^T,
+ * a symmetric 4 x 4 matrix per pixel, alpha included (the 0.5 of x and the 2 of out cancel).  The covariance is taken about the
+ * nearest slot, E[(c - c_r)(c - c_r)^T] - E[c - c_r] E[c - c_r]^T, so it does not cancel where one colour dominates.  n = 0:
+ * dimg = g bit for bit.  g, dimg: dense f32, 16-byte aligned; every pixel of dimg written.  Per pixel, as the forward. */
+int p2p_palette_project_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                            const float* g, float* dimg, void* stream);
+
 /* ---- differentiable augmentation (build-added, DESIGN.md "differentiable augmentation") --------------------------- */
 /* DiffAugment (Zhao et al., NeurIPS 2020) of dense f32 RGBA images [N][H][W][4], 16-byte aligned, any H, W >= 1 (H * W <= 2^28,
  * N <= 65535).  color: f32 [N][3] = brightness offset b, saturation factor s, contrast factor k; geometry: int32 [N][4] = ty, tx,

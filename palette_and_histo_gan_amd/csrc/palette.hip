@@ -5,7 +5,8 @@
 // Vector-ALU and exponential bound (H*W*K pair evaluations per image), no matrix work.  The image's palette sits in LDS as one
 // float4 per slot (4 KB); the slot loops read it at a wave-uniform address (broadcast, one ds_read_b128 per slot shared by the
 // lane's pixels); every lane owns its own pixels.  All reductions run in a fixed order (no float atomics): bit-reproducible.
-// p2p_palette_snap, further down, is the hard counterpart in integer arithmetic (nearest slot, lowest index on ties).
+// p2p_palette_snap, further down, is the hard counterpart in integer arithmetic (nearest slot, lowest index on ties);
+// p2p_palette_project_fwd / _bwd, after it, replace every pixel by a palette colour, differentiably.
 #include "p2p_common.hpp"
 
 #define PAL_MAX 256
@@ -289,6 +290,35 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_extract_kernel(int HW, co
 #define PAL_SNAP_PIX 4
 #define PAL_SNAP_BIAS 520200u
 
+// The packed-key code that p2p_palette_snap and the hard forward of p2p_palette_project_fwd share, so that their bits cannot drift
+// apart: the pixel's packed bytes, the slots in LDS (returns the clamped slot count; the caller synchronises), one step of the
+// unsigned min, and the normalised colour of a slot's packed bytes.
+__device__ __forceinline__ unsigned pal_snap_quant(const float4& v) {
+    return pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
+}
+
+__device__ __forceinline__ int pal_snap_load(const int* __restrict__ palette, const int* __restrict__ sizes, int b, int K, uint2* slot) {
+    int n = sizes[b];
+    n = n < 0 ? 0 : (n > K ? K : n);
+    for (int k = threadIdx.x; k < n; k += PAL_THREADS) {
+        const int4 c = *(const int4*)(palette + ((long long)b * K + k) * 4);
+        const unsigned cx = (unsigned)c.x & 255u, cy = (unsigned)c.y & 255u, cz = (unsigned)c.z & 255u, cw = (unsigned)c.w & 255u;
+        const unsigned pk = cx | (cy << 8) | (cz << 16) | (cw << 24);
+        slot[k] = make_uint2(pk, ((cx * cx + cy * cy + cz * cz + cw * cw + PAL_SNAP_BIAS) << 8) | (unsigned)k);
+    }
+    return n;
+}
+
+__device__ __forceinline__ unsigned pal_snap_min(unsigned key, unsigned q, const uint2& s) {
+    const unsigned k2 = s.y - (__builtin_amdgcn_udot4(q, s.x, 0u, false) << 9);
+    return k2 < key ? k2 : key;
+}
+
+__device__ __forceinline__ float4 pal_snap_colour(unsigned c) {
+    return make_float4(__fsub_rn(__fdiv_rn((float)(c & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)((c >> 8) & 255u), 127.5f), 1.0f),
+                       __fsub_rn(__fdiv_rn((float)((c >> 16) & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)(c >> 24), 127.5f), 1.0f));
+}
+
 __global__ __launch_bounds__(PAL_THREADS) void palette_snap_clear_kernel(long long n_counts, int* __restrict__ counts, long long n_stats,
                                                                          long long* __restrict__ stats) {
     const long long i = (long long)blockIdx.x * PAL_THREADS + threadIdx.x;
@@ -304,15 +334,8 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const
     __shared__ int cnt[PAL_MAX];
     __shared__ unsigned sums[2];             // off-palette pixels and summed distances of the workgroup (<= 1024 * 260100 < 2^32)
     const int b = blockIdx.y, tid = threadIdx.x;
-    int n = sizes[b];
-    n = n < 0 ? 0 : (n > K ? K : n);
-    for (int k = tid; k < n; k += PAL_THREADS) {
-        const int4 c = *(const int4*)(palette + ((long long)b * K + k) * 4);
-        const unsigned cx = (unsigned)c.x & 255u, cy = (unsigned)c.y & 255u, cz = (unsigned)c.z & 255u, cw = (unsigned)c.w & 255u;
-        const unsigned pk = cx | (cy << 8) | (cz << 16) | (cw << 24);
-        slot[k] = make_uint2(pk, ((cx * cx + cy * cy + cz * cz + cw * cw + PAL_SNAP_BIAS) << 8) | (unsigned)k);
-        cnt[k] = 0;
-    }
+    const int n = pal_snap_load(palette, sizes, b, K, slot);
+    for (int k = tid; k < n; k += PAL_THREADS) cnt[k] = 0;
     if (tid < 2) sums[tid] = 0u;
     __syncthreads();
     const long long base = (long long)b * HW;
@@ -331,17 +354,14 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const
             if (dist_out) dist_out[base + p] = 0;
             if (image_out) *(float4*)(image_out + (base + p) * 4) = v;
         }
-        q[j] = pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
+        q[j] = pal_snap_quant(v);
     }
     if (n == 0) return;                      // the whole workgroup; counts and stats stay 0
 #pragma unroll 4
     for (int k = 0; k < n; ++k) {
         const uint2 s = slot[k];             // wave-uniform address: one broadcast ds_read_b64 for the lane's pixels
 #pragma unroll
-        for (int j = 0; j < PAL_SNAP_PIX; ++j) {
-            const unsigned k2 = s.y - (__builtin_amdgcn_udot4(q[j], s.x, 0u, false) << 9);
-            key[j] = k2 < key[j] ? k2 : key[j];
-        }
+        for (int j = 0; j < PAL_SNAP_PIX; ++j) key[j] = pal_snap_min(key[j], q[j], s);
     }
     unsigned off = 0u, dsum = 0u;
 #pragma unroll
@@ -352,12 +372,7 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const
         const unsigned d = (key[j] >> 8) - PAL_SNAP_BIAS + __builtin_amdgcn_udot4(q[j], q[j], 0u, false);
         index_out[base + p] = idx;
         if (dist_out) dist_out[base + p] = (int)d;
-        if (image_out) {
-            const unsigned c = slot[idx].x;
-            *(float4*)(image_out + (base + p) * 4) =
-                make_float4(__fsub_rn(__fdiv_rn((float)(c & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)((c >> 8) & 255u), 127.5f), 1.0f),
-                            __fsub_rn(__fdiv_rn((float)((c >> 16) & 255u), 127.5f), 1.0f), __fsub_rn(__fdiv_rn((float)(c >> 24), 127.5f), 1.0f));
-        }
+        if (image_out) *(float4*)(image_out + (base + p) * 4) = pal_snap_colour(slot[idx].x);
         atomicAdd(&cnt[idx], 1);
         off += d > 0u ? 1u : 0u;
         dsum += d;
@@ -375,6 +390,199 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const
     for (int k = tid; k < n; k += PAL_THREADS)
         if (cnt[k]) atomicAdd(counts + (long long)b * K + k, cnt[k]);
     if (tid < 2 && sums[tid]) atomicAdd((unsigned long long*)(stats + (long long)b * 2 + tid), (unsigned long long)sums[tid]);
+}
+
+// Differentiable palette projection (DESIGN.md "palette projection"): every pixel replaced by a colour of its image's palette, on the
+// grid of the kernels above (a workgroup owns PAL_THREADS * PAL_PROJ_PIX consecutive pixels of one image).  Purely per pixel: no
+// workspace, no atomics, no cross-lane traffic, so a pixel's bits depend on nothing but the pixel and its image's palette.
+//   soft forward: y = 2 sum_k w_k c_k - 1 with the w of the soft histogram; sum_k w_k c_k is taken as c_r + E[c - c_r] about the
+//                 nearest slot r (first index of min_k d), so a pixel on a palette colour returns that colour to rounding;
+//   hard forward: the snap's packed key (pal_snap_* above) and nothing else: the bits of p2p_palette_snap's image_out;
+//   backward:     dimg = (2 / tau) Cov_w(c) g at the raw image (the 0.5 of x = img 0.5 + 0.5 and the 2 of y cancel), the 4 x 4 covariance
+//                 about r: E[(c - c_r)(c - c_r)^T] - E[c - c_r] E[c - c_r]^T.  About r the dominant slot's terms are exactly 0 and the
+//                 rest is small times small, as in soft_palette_bwd_kernel; the covariance as written cancels to rounding in f32.
+// An image without valid slots passes through: the forward copies img, the backward copies g, bit for bit.
+#define PAL_PROJ_PIX 4
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_project_soft_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                           const int* __restrict__ sizes, int K, float nscale,
+                                                                           float* __restrict__ out) {
+    __shared__ float4 c[PAL_MAX];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = pal_load(palette, sizes, b, K, c);
+    const long long base = (long long)b * HW;
+    int pix[PAL_PROJ_PIX];
+    bool valid[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        pix[j] = (blockIdx.x * PAL_PROJ_PIX + j) * PAL_THREADS + tid;
+        valid[j] = pix[j] < HW;
+    }
+    if (n == 0) {                            // the whole workgroup
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j)
+            if (valid[j]) *(float4*)(out + (base + pix[j]) * 4) = *(const float4*)(img + (base + pix[j]) * 4);
+        return;
+    }
+    float4 x[PAL_PROJ_PIX];
+    float mn[PAL_PROJ_PIX];
+    int r[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        x[j] = valid[j] ? pal_x(img, base + pix[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        mn[j] = INFINITY;
+        r[j] = 0;
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+            const float d = pal_dist(x[j], ck);
+            if (d < mn[j]) { mn[j] = d; r[j] = k; }
+        }
+    }
+    float4 cr[PAL_PROJ_PIX], Ec[PAL_PROJ_PIX];
+    float S[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        cr[j] = c[r[j]];
+        S[j] = 0.f;
+        Ec[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+            const float e = __builtin_amdgcn_exp2f((pal_dist(x[j], ck) - mn[j]) * nscale);
+            S[j] += e;
+            Ec[j].x = __fmaf_rn(e, ck.x - cr[j].x, Ec[j].x); Ec[j].y = __fmaf_rn(e, ck.y - cr[j].y, Ec[j].y);
+            Ec[j].z = __fmaf_rn(e, ck.z - cr[j].z, Ec[j].z); Ec[j].w = __fmaf_rn(e, ck.w - cr[j].w, Ec[j].w);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        if (!valid[j]) continue;
+        const float is = 1.f / S[j];                              // S >= 1: the nearest slot contributes exp2(0)
+        *(float4*)(out + (base + pix[j]) * 4) =
+            make_float4(__fmaf_rn(2.f, __fmaf_rn(Ec[j].x, is, cr[j].x), -1.f), __fmaf_rn(2.f, __fmaf_rn(Ec[j].y, is, cr[j].y), -1.f),
+                        __fmaf_rn(2.f, __fmaf_rn(Ec[j].z, is, cr[j].z), -1.f), __fmaf_rn(2.f, __fmaf_rn(Ec[j].w, is, cr[j].w), -1.f));
+    }
+}
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_project_hard_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                           const int* __restrict__ sizes, int K, float* __restrict__ out) {
+    __shared__ uint2 slot[PAL_MAX];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = pal_snap_load(palette, sizes, b, K, slot);
+    __syncthreads();
+    const long long base = (long long)b * HW;
+    unsigned q[PAL_PROJ_PIX], key[PAL_PROJ_PIX];
+    bool valid[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        const int p = (blockIdx.x * PAL_PROJ_PIX + j) * PAL_THREADS + tid;
+        valid[j] = p < HW;
+        q[j] = 0u;
+        key[j] = 0xFFFFFFFFu;
+        if (!valid[j]) continue;
+        const float4 v = *(const float4*)(img + (base + p) * 4);
+        if (n == 0) *(float4*)(out + (base + p) * 4) = v;
+        q[j] = pal_snap_quant(v);
+    }
+    if (n == 0) return;                      // the whole workgroup
+#pragma unroll 4
+    for (int k = 0; k < n; ++k) {
+        const uint2 s = slot[k];
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j) key[j] = pal_snap_min(key[j], q[j], s);
+    }
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        if (!valid[j]) continue;
+        const int p = (blockIdx.x * PAL_PROJ_PIX + j) * PAL_THREADS + tid;
+        *(float4*)(out + (base + p) * 4) = pal_snap_colour(slot[key[j] & 255u].x);
+    }
+}
+
+// centred second moments of a pixel, the upper triangle of a symmetric 4 x 4 matrix
+struct PalMoments { float xx, xy, xz, xw, yy, yz, yw, zz, zw, ww; };
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_project_bwd_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
+                                                                          const int* __restrict__ sizes, int K, float nscale, float two_over_tau,
+                                                                          const float* __restrict__ g, float* __restrict__ dimg) {
+    __shared__ float4 c[PAL_MAX];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = pal_load(palette, sizes, b, K, c);
+    const long long base = (long long)b * HW;
+    int pix[PAL_PROJ_PIX];
+    bool valid[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        pix[j] = (blockIdx.x * PAL_PROJ_PIX + j) * PAL_THREADS + tid;
+        valid[j] = pix[j] < HW;
+    }
+    if (n == 0) {                            // the whole workgroup: the forward was a copy
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j)
+            if (valid[j]) *(float4*)(dimg + (base + pix[j]) * 4) = *(const float4*)(g + (base + pix[j]) * 4);
+        return;
+    }
+    float4 x[PAL_PROJ_PIX];
+    float mn[PAL_PROJ_PIX];
+    int r[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        x[j] = valid[j] ? pal_x(img, base + pix[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        mn[j] = INFINITY;
+        r[j] = 0;
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+            const float d = pal_dist(x[j], ck);
+            if (d < mn[j]) { mn[j] = d; r[j] = k; }
+        }
+    }
+    float4 cr[PAL_PROJ_PIX], m1[PAL_PROJ_PIX];
+    PalMoments m2[PAL_PROJ_PIX];
+    float S[PAL_PROJ_PIX];
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        cr[j] = c[r[j]];
+        S[j] = 0.f;
+        m1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        m2[j] = PalMoments{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    }
+    for (int k = 0; k < n; ++k) {
+        const float4 ck = c[k];
+#pragma unroll
+        for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+            const float e = __builtin_amdgcn_exp2f((pal_dist(x[j], ck) - mn[j]) * nscale);
+            const float cx = ck.x - cr[j].x, cy = ck.y - cr[j].y, cz = ck.z - cr[j].z, cw = ck.w - cr[j].w;
+            const float ex = e * cx, ey = e * cy, ez = e * cz, ew = e * cw;
+            S[j] += e;
+            m1[j].x += ex; m1[j].y += ey; m1[j].z += ez; m1[j].w += ew;
+            m2[j].xx = __fmaf_rn(ex, cx, m2[j].xx); m2[j].xy = __fmaf_rn(ex, cy, m2[j].xy); m2[j].xz = __fmaf_rn(ex, cz, m2[j].xz);
+            m2[j].xw = __fmaf_rn(ex, cw, m2[j].xw); m2[j].yy = __fmaf_rn(ey, cy, m2[j].yy); m2[j].yz = __fmaf_rn(ey, cz, m2[j].yz);
+            m2[j].yw = __fmaf_rn(ey, cw, m2[j].yw); m2[j].zz = __fmaf_rn(ez, cz, m2[j].zz); m2[j].zw = __fmaf_rn(ez, cw, m2[j].zw);
+            m2[j].ww = __fmaf_rn(ew, cw, m2[j].ww);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < PAL_PROJ_PIX; ++j) {
+        if (!valid[j]) continue;
+        const float is = 1.f / S[j];
+        const float ax = m1[j].x * is, ay = m1[j].y * is, az = m1[j].z * is, aw = m1[j].w * is;
+        const PalMoments& m = m2[j];
+        const float vxx = m.xx * is - ax * ax, vxy = m.xy * is - ax * ay, vxz = m.xz * is - ax * az, vxw = m.xw * is - ax * aw;
+        const float vyy = m.yy * is - ay * ay, vyz = m.yz * is - ay * az, vyw = m.yw * is - ay * aw;
+        const float vzz = m.zz * is - az * az, vzw = m.zw * is - az * aw, vww = m.ww * is - aw * aw;
+        const float4 u = *(const float4*)(g + (base + pix[j]) * 4);
+        *(float4*)(dimg + (base + pix[j]) * 4) =
+            make_float4(two_over_tau * (vxx * u.x + vxy * u.y + vxz * u.z + vxw * u.w), two_over_tau * (vxy * u.x + vyy * u.y + vyz * u.z + vyw * u.w),
+                        two_over_tau * (vxz * u.x + vyz * u.y + vzz * u.z + vzw * u.w), two_over_tau * (vxw * u.x + vyw * u.y + vzw * u.z + vww * u.w));
+    }
 }
 
 static inline int pal_chunks(int H, int W, int per_lane) {
@@ -430,6 +638,28 @@ extern "C" int p2p_palette_snap(int N, int H, int W, const float* img, const int
     palette_snap_kernel<<<dim3(pal_chunks(H, W, PAL_SNAP_PIX), N), PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, index_out, image_out,
                                                                                           dist_out, counts_out, stats_out);
     return p2p_check_launch("p2p_palette_snap");
+}
+
+extern "C" int p2p_palette_project_fwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau, int hard,
+                                       float* out, void* stream) {
+    if (pal_check("p2p_palette_project_fwd", N, H, W, img, palette, sizes, K, tau)) return -1;
+    P2P_REQUIRE(hard == 0 || hard == 1, "p2p_palette_project_fwd: hard = %d, expected 0 (soft) or 1 (snap)", hard);
+    P2P_REQUIRE(out && ((uintptr_t)out % 16) == 0, "p2p_palette_project_fwd: out is a null pointer or not 16-byte aligned");
+    const dim3 grid(pal_chunks(H, W, PAL_PROJ_PIX), N);
+    hipStream_t st = (hipStream_t)stream;
+    if (hard) palette_project_hard_kernel<<<grid, PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, out);
+    else palette_project_soft_kernel<<<grid, PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, (float)(-1.4426950408889634 / (double)tau), out);
+    return p2p_check_launch("p2p_palette_project_fwd");
+}
+
+extern "C" int p2p_palette_project_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                                       const float* g, float* dimg, void* stream) {
+    if (pal_check("p2p_palette_project_bwd", N, H, W, img, palette, sizes, K, tau)) return -1;
+    P2P_REQUIRE(g && dimg && ((uintptr_t)g % 16) == 0 && ((uintptr_t)dimg % 16) == 0,
+                "p2p_palette_project_bwd: g or dimg is a null pointer or not 16-byte aligned");
+    palette_project_bwd_kernel<<<dim3(pal_chunks(H, W, PAL_PROJ_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
+        H * W, img, palette, sizes, K, (float)(-1.4426950408889634 / (double)tau), (float)(2.0 / (double)tau), g, dimg);
+    return p2p_check_launch("p2p_palette_project_bwd");
 }
 
 extern "C" int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* palette_out, int* sizes_out, void* stream) {

@@ -7,8 +7,10 @@ respect to the image: one torch.autograd.Function whose backward is HIP as well 
 engine.train_step_rgba_hooked or a tf.GradientTape step written with it reaches the generator.  `palette_histogram_loss` is a
 handful of torch ops on the (B, K) result.  `snap_to_palette` is the hard counterpart (p2p_palette_snap: every pixel's nearest
 palette colour in exact integer arithmetic, per-slot counts, off-palette pixels), not differentiable, for inference
-(Pix2PixModel.generate(snap=)) and evaluation (`palette_metrics`, S2SModel.report_palette).  All kernels launch on the current
-stream; there is no CPU path.
+(Pix2PixModel.generate(snap=)) and evaluation (`palette_metrics`, S2SModel.report_palette).  `project_to_palette` stands between the two: it replaces every pixel by a
+palette colour -- the soft expected colour or the snap itself -- and IS differentiable (p2p_palette_project_fwd / _bwd: the exact
+Jacobian of the soft projection, or the straight-through identity), so a tape step can show the discriminator what survives the snap
+(Pix2PixPaletteSnapModel).  All kernels launch on the current stream; there is no CPU path.
 
 The default temperature 1e-3 makes a pixel that sits on a palette colour count for that slot alone (two colours one 8-bit step apart
 in one channel are 1.5e-5 apart in d, a weight ratio of 0.985; a pixel half-way between two clearly different colours is shared).
@@ -142,6 +144,79 @@ def soft_palette_histogram(image_batch, palette, sizes=None, temperature=1e-3, d
     pal, sz = _palette_args(pal, sizes, B, dev)
     with torch.cuda.device(dev):
         return SoftPaletteHistogram.apply(img, pal, sz, temperature)
+
+
+def _checked_temperature(temperature):
+    temperature = float(temperature)
+    if not 0.0 < temperature < float("inf"):
+        raise ValueError(f"the temperature must be positive and finite, got {temperature}")
+    return temperature
+
+
+def check_projection_mode(hard, gradient):
+    """the (forward, backward) pairs project_to_palette accepts"""
+    if gradient not in ("soft", "identity"):
+        raise ValueError(f'gradient is "soft" or "identity", got {gradient!r}')
+    if not hard and gradient == "identity":
+        raise ValueError('hard=False with gradient="identity": the soft forward has an exact gradient (gradient="soft"); the '
+                         'straight-through identity belongs to the hard forward')
+
+
+class PaletteProjection(torch.autograd.Function):
+    """img: dense f32 (B, H, W, 4) device tensor; palette int32 (B, K, 4), sizes int32 (B,), both dense on img's device ->
+    projected image (B, H, W, 4).  Backward: with respect to img only, single backward; with `soft_gradient` the VJP of the soft
+    projection at img (p2p_palette_project_bwd), without it the upstream gradient itself: nothing saved, nothing launched."""
+
+    @staticmethod
+    def forward(ctx, img, palette, sizes, tau, hard, soft_gradient):
+        B, H, W, _ = (int(x) for x in img.shape)
+        K = int(palette.shape[1])
+        out = torch.empty_like(img)
+        L.call("p2p_palette_project_fwd", B, H, W, _p(img), _p(palette), _p(sizes), K, tau, int(hard), _p(out), _stream(img.device))
+        ctx.soft_gradient = soft_gradient
+        if soft_gradient and ctx.needs_input_grad[0]:
+            ctx.save_for_backward(img, palette, sizes)
+            ctx.tau = tau
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.soft_gradient:
+            return grad_out, None, None, None, None, None
+        img, palette, sizes = ctx.saved_tensors
+        B, H, W, _ = (int(x) for x in img.shape)
+        K = int(palette.shape[1])
+        dev = img.device
+        g = grad_out.to(torch.float32).contiguous()
+        dimg = torch.empty_like(img)
+        with torch.cuda.device(dev):
+            L.call("p2p_palette_project_bwd", B, H, W, _p(img), _p(palette), _p(sizes), K, ctx.tau, _p(g), _p(dimg), _stream(dev))
+        return dimg, None, None, None, None, None
+
+
+def project_to_palette(image_batch, palette, sizes=None, temperature=5e-2, hard=False, gradient="soft", device=None):
+    """A (B, H, W, 4) batch in [-1, 1] with every pixel replaced by a colour of its image's palette (B, K <= 256, 4) of 0..255 RGBA
+    rows, of which the first sizes[b] are valid (None: all K); f32, differentiable with respect to `image_batch` only.
+    With w_pk the weights of soft_palette_histogram at `temperature` and c_k = palette_k / 255:
+        hard=False   y_p = 2 sum_k w_pk c_k - 1: the expected palette colour, alpha included
+        hard=True    y_p = snap_to_palette(image_batch, palette, sizes).image_p, bit for bit
+        gradient="soft"       dL/dimg_p = (2 / temperature) Cov_w(c) dL/dy_p, the exact Jacobian of the soft projection at the raw
+                              image -- for hard=True a surrogate: the snap's own gradient is 0 almost everywhere
+        gradient="identity"   dL/dimg = dL/dy (straight-through; hard=True only; nothing is saved or launched in backward)
+    An image with sizes[b] <= 0 (extract_palette_batch's -1 included) passes through: its pixels and its gradient are copied.
+    The default temperature 5e-2 is the soft histogram's coarse setting: at 1e-3 the soft gradient vanishes at every pixel that is
+    not within ~0.03 of the midway plane between two colours."""
+    L.lib()          # fail loudly if the HIP library is missing: there is no CPU path
+    check_projection_mode(hard, gradient)
+    dev = _device_of(image_batch, device)
+    img = _rgba(image_batch, dev)
+    B = int(img.shape[0])
+    pal = _checked_palette(palette, B)
+    temperature = _checked_temperature(temperature)
+    pal, sz = _palette_args(pal, sizes, B, dev)
+    with torch.cuda.device(dev):
+        return PaletteProjection.apply(img, pal, sz, temperature, bool(hard), gradient == "soft")
 
 
 PaletteSnap = collections.namedtuple("PaletteSnap", "index image distance counts off_palette distance_sum")

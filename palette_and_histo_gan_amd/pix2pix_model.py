@@ -6,6 +6,7 @@
     Pix2PixIndexedModel(train_ds, test_ds, model_name, architecture_name, lambda_segmentation=0.5)
     Pix2PixPaletteModel(..., lambda_l1, lambda_palette, lambda_conformance=0.0, temperature=1e-3)      -- build-added
     Pix2PixDiffAugmentModel(..., lambda_l1, policy="color,translation,cutout")                         -- build-added
+    Pix2PixPaletteSnapModel(..., lambda_l1, hard=True, gradient="identity", temperature=5e-2)          -- build-added
 
 The constructor follows the reference's (pix2pix_model.py:12-36): create_generator() / create_discriminator() with the
 reference's builder signatures, `loss_object`, two Adam(0.0002, beta_1=0.5) optimizers, `checkpoint`,
@@ -449,6 +450,58 @@ class Pix2PixDiffAugmentModel(Pix2PixModel):
     def train_step(self, batch, step, update_steps):
         source_image, real_image = batch
         g_loss, d_loss, _, _ = self.augmented_step(source_image, real_image, step)
+        self._log(g_loss, d_loss, step, update_steps)
+        return g_loss, d_loss
+
+
+class Pix2PixPaletteSnapModel(Pix2PixModel):
+    """Build-added (no counterpart in the reference): the RGBA model trained THROUGH the palette snap.  generate(snap="target")
+    repairs a generated sprite after training; here the repair is part of the step: the fake image is projected onto the palette
+    of the real image (palette.project_to_palette) before the discriminator judges it, so the discriminator sees what inference
+    will return and the generator is trained on what survives the snap.  `hard` / `gradient` / `temperature` choose the projection:
+    (True, "identity") is the snap with the straight-through gradient, (True, "soft") the snap with the soft projection's Jacobian,
+    (False, "soft") the soft projection with its exact gradient.  The real image lies on its own palette and is not projected; the
+    L1 term is taken on the un-projected fake image.  An image whose target has more than MAX_PALETTE_SIZE colours passes through.
+
+    train_step is the reference's step (pix2pix_model.py:62-89) written for tf.GradientTape, as Pix2PixDiffAugmentModel's: one GPU,
+    not replayed.  generate() and the report_* evaluations are inherited; generate(batch, snap="target") is the matching inference
+    call."""
+
+    def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, hard=True, gradient="identity", temperature=5e-2,
+                 **kw):
+        _palette.check_projection_mode(hard, gradient)          # a pair without a meaning fails here, not at the first step
+        if not 0.0 < float(temperature) < float("inf"):
+            raise ValueError(f"the temperature must be positive and finite, got {temperature}")
+        super().__init__(train_ds, test_ds, model_name, architecture_name, lambda_l1, **kw)
+        self.hard, self.gradient, self.temperature = bool(hard), gradient, float(temperature)
+
+    def projected_step(self, source_image, real_image, step, masks=None, apply=True):
+        """one step: (g_loss, d_loss, generator gradients, discriminator gradients, projected fake image), both gradients taken at
+        the pre-update weights.  masks: injected dropout keep-masks instead of the device's draw; apply=False leaves the weights
+        alone.  (`step` is not used: the projection has no random part.)"""
+        from .tape import GradientTape
+        source_image, real_image = self._upload([source_image, real_image])
+        palette, sizes = _palette.extract_palette_batch(real_image, check=False, device=self.engine.device)      # no host sync
+        with GradientTape(persistent=True) as tape:
+            fake_image = self.generator(source_image, training=True, masks=masks)
+            projected_fake = _palette.project_to_palette(fake_image, palette, sizes, self.temperature, self.hard, self.gradient,
+                                                         device=self.engine.device)
+            real_predicted = self.discriminator([real_image, source_image], training=True)
+            fake_predicted = self.discriminator([projected_fake, source_image], training=True)
+            g_loss = self.generator_loss(fake_predicted, fake_image, real_image)
+            d_loss = self.discriminator_loss(real_predicted, fake_predicted)
+        generator_gradients = tape.gradient(g_loss[0], self.generator.trainable_variables)
+        discriminator_gradients = tape.gradient(d_loss[0], self.discriminator.trainable_variables)
+        if apply:
+            self.generator_optimizer.apply_gradients(zip(generator_gradients, self.generator.trainable_variables))
+            self.discriminator_optimizer.apply_gradients(zip(discriminator_gradients, self.discriminator.trainable_variables))
+        tape.release()
+        return (tuple(x.detach() for x in g_loss), tuple(x.detach() for x in d_loss), generator_gradients, discriminator_gradients,
+                projected_fake.detach())
+
+    def train_step(self, batch, step, update_steps):
+        source_image, real_image = batch
+        g_loss, d_loss, _, _, _ = self.projected_step(source_image, real_image, step)
         self._log(g_loss, d_loss, step, update_steps)
         return g_loss, d_loss
 

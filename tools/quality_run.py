@@ -14,6 +14,10 @@ trains to the same quality as the f32 parity mode.   python tools/quality_run.py
 and 5e-2, and one with lambda_conformance = 1 alone, all bf16 on the same pairs, steps and seed, each reporting report_l1() and
 report_palette() (share of generated pixels off the target's palette, their RMS distance to it, histogram total variation).
 `--dtypes ""` runs that leg alone.
+
+--snap-train adds a third leg on the same pairs and seed in bf16, 2 520 steps unless --steps says otherwise: the
+plain RGBA model and Pix2PixPaletteSnapModel at (hard, identity), (hard, soft gradient, tau = 5e-2) and (soft forward, tau = 5e-2),
+each reporting report_l1(), report_palette() and the L1 of generate(snap="target") -- what inference with the repair returns.
 """
 import argparse
 import contextlib
@@ -73,11 +77,16 @@ def make_sets(n_train=250, n_test=44, seed=47):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10080)          # ceil(250 / 4) * 160 (experiments.ipynb:268)
+    ap.add_argument("--steps", type=int, default=None, help="default 10080 = ceil(250 / 4) * 160 (experiments.ipynb:268); "
+                                                            "the --snap-train leg alone defaults to 2520")
     ap.add_argument("--update-steps", type=int, default=252)
     ap.add_argument("--dtypes", default="f32,bf16")
     ap.add_argument("--palette", action="store_true", help="also train the four models of the palette-loss comparison")
+    ap.add_argument("--snap-train", action="store_true", help="also train the four models of the train-through-the-snap comparison")
     args = ap.parse_args()
+    snap_steps = args.steps if args.steps is not None else 2520
+    if args.steps is None:
+        args.steps = 10080
     (tr_s, tr_t), (te_s, te_t) = make_sets()
     os.makedirs(os.path.join(ROOT, "gpurun_out", "quality"), exist_ok=True)
     os.chdir(os.path.join(ROOT, "gpurun_out", "quality"))       # fit() writes its logs and checkpoints under ./temp-side2side
@@ -111,6 +120,8 @@ def main():
                               "l1_test_ratio": out["bf16"]["l1_test"] / out["f32"]["l1_test"]}
     if args.palette:
         out["palette"] = palette_leg(args, (tr_s, tr_t), (te_s, te_t))
+    if args.snap_train:
+        out["snap_train"] = snap_train_leg(snap_steps, args.update_steps, (tr_s, tr_t), (te_s, te_t))
     print(json.dumps(out))
 
 
@@ -139,6 +150,51 @@ def palette_leg(args, train_pairs, test_pairs):
                      "wall_s": round(wall, 1), **kw}
         print(f"[{name}] L1 {float(l1_train):.5f} / {float(l1_test):.5f}, off-palette {p_train['off_palette']:.5f} / "
               f"{p_test['off_palette']:.5f} (train/test), {wall:.1f} s", file=sys.stderr, flush=True)
+    return res
+
+
+SNAP_TRAIN_RUNS = [("rgba", None),
+                   ("hard, identity", {"hard": True, "gradient": "identity"}),
+                   ("hard, soft tau=5e-2", {"hard": True, "gradient": "soft", "temperature": 5e-2}),
+                   ("soft tau=5e-2", {"hard": False, "gradient": "soft", "temperature": 5e-2})]
+
+
+def snapped_l1(model, num_images=44):
+    """(train, test) L1 of generate(snap="target") over the samples report_l1 evaluates: the first num_images, as batches of one"""
+    res = []
+    for ds in (model.train_ds, model.test_ds):
+        real, fake = [], []
+        for batch in model._whole(ds).unbatch().take(num_images).batch(1):
+            target = batch[1][0]
+            real.append((target.detach().cpu() if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))).to(torch.float32))
+            fake.append(model.generate(batch, snap="target")[0].to(torch.float32).cpu())
+        res.append(float(model.evaluate_l1(torch.stack(real), torch.stack(fake))))
+    return res
+
+
+def snap_train_leg(steps, update_steps, train_pairs, test_pairs):
+    """the four bf16 models of DESIGN.md 6e on the same pairs, steps and seed"""
+    res = {"steps": steps}
+    for name, kw in SNAP_TRAIN_RUNS:
+        train = D.SpriteRGBADataset(*train_pairs, augment=False, batch_size=4, seed=47)
+        test = D.SpriteRGBADataset(*test_pairs, augment=False, batch_size=4, seed=48)
+        t0 = time.time()
+        with contextlib.redirect_stdout(sys.stderr):
+            tag = "quality-snap-" + name.replace(" ", "-").replace(",", "").replace("=", "")
+            if kw is None:
+                model = M.Pix2PixModel(train, test, "front2right", tag, lambda_l1=100.0, dtype="bf16", seed=47)
+            else:
+                model = M.Pix2PixPaletteSnapModel(train, test, "front2right", tag, lambda_l1=100.0, dtype="bf16", seed=47, **kw)
+            model.fit(steps, update_steps)
+            torch.cuda.synchronize()
+            wall = time.time() - t0
+            l1_train, l1_test = model.report_l1(44)
+            p_train, p_test = model.report_palette(44)
+            s_train, s_test = snapped_l1(model)
+        res[name] = {"l1_train": float(l1_train), "l1_test": float(l1_test), "palette_train": p_train, "palette_test": p_test,
+                     "l1_snapped_train": s_train, "l1_snapped_test": s_test, "wall_s": round(wall, 1), **(kw or {})}
+        print(f"[{name}] L1 {float(l1_train):.5f} / {float(l1_test):.5f}, off-palette {p_train['off_palette']:.5f} / "
+              f"{p_test['off_palette']:.5f}, L1 snapped {s_train:.5f} / {s_test:.5f} (train/test), {wall:.1f} s", file=sys.stderr, flush=True)
     return res
 
 
