@@ -14,12 +14,13 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 
 def source_fingerprint():
     """sha256 over everything that decides which kernels a step launches and what they do (csrc/, the C ABI header, the
-    engine).  Counter profiles under profiles/ are stamped with it; bench.py only quotes a profile whose stamp matches the
-    tree it runs from (the GPU box has no .git)."""
+    engine and the two modules split out of it).  Counter profiles under profiles/ are stamped with it; bench.py only quotes a
+    profile whose stamp matches the tree it runs from (the GPU box has no .git)."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp")))
-    files += [os.path.join(os.path.dirname(HERE), "include", "p2pgan.h"), os.path.join(HERE, "engine.py")]
+    files.append(os.path.join(os.path.dirname(HERE), "include", "p2pgan.h"))
+    files += [os.path.join(HERE, f) for f in ("buffers.py", "engine.py", "replay_pack.py")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

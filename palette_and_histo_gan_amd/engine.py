@@ -1,14 +1,14 @@
 """Device engine of the Pix2Pix side2side training step on MI355X.
 
-Owns the HBM layout (haloed NHWC activation buffers, concat-by-slice, flat f32 parameter / gradient /
-Adam buffers, per-layer weight copies for the MFMA kernels) and issues the HIP kernels of
-libp2pgan_hip.so in the order of the reference's train_step (pix2pix_model.py:62-89, 295-325).  PyTorch
-tensors are only device-memory holders here; every arithmetic op on the path is a call into the C ABI
-(include/p2pgan.h).  There is no CPU fallback.
+Issues the HIP kernels of libp2pgan_hip.so in the order of the reference's train_step (pix2pix_model.py:62-89, 295-325) on the
+HBM layout of buffers.py (haloed NHWC activation buffers, concat-by-slice, flat f32 parameter / gradient / Adam buffers, per-layer
+weight copies for the MFMA kernels); a recorded step is packed by replay_pack.py.  PyTorch tensors are only device-memory holders
+here; every arithmetic op on the path is a call into the C ABI (include/p2pgan.h).  There is no CPU fallback.
 """
 from collections import OrderedDict
 import ctypes as C
 import math
+import operator
 import os
 
 import numpy as np
@@ -16,18 +16,82 @@ import torch
 
 from . import _lib as L
 from . import histogram as _histogram
+from .buffers import (HALO, DOWN_FILTERS, UP_FILTERS, NULL, DenseBuf, HaloBuf, LayerW, ParamStore, _p, _torch_dtype,  # noqa: F401
+                      discriminator_param_shapes, generator_param_shapes, pad8, up32)
+from .replay_pack import ReplayCall, _pack_arg, pack_replay  # noqa: F401
 
-HALO = 2
 IN_EPS = 1e-3           # tfa InstanceNormalization default (networks.py:18,29)
 LEAKY_ALPHA = 0.3       # keras LeakyReLU default (networks.py:19)
-DOWN_FILTERS = (64, 128, 256, 512, 512, 512)      # networks.py:57-64
-UP_FILTERS = (512, 512, 256, 128, 64, 32)         # networks.py:66-73
 UP_DROPOUT = (True, True, True, False, False, False)
 MAX_PALETTE_SIZE = 256
 
 
-def _torch_dtype(dtype):
-    return torch.float32 if dtype == L.F32 else torch.bfloat16
+def _flag(text):
+    return text != "0"
+
+
+# The A/B switches of the engine: (attribute, environment variable or None, default, parser of the variable's text).  __init__ sets
+# every attribute from this table -- nothing else in this file reads the environment -- and tests, tools and bench.py assign them
+# as plain attributes ("side.x": attribute x of the weight-gradient stream helper).
+# SWITCHES choose kernels, K splits and grids: a recorded step holds those choices BY VALUE, so _replay_key takes every one of them
+# from this same table -- a switch added here cannot be forgotten there and let a stale recording replay the wrong kernels.
+SWITCHES = (
+    ("use_conv_fewout", "P2P_CONV_FEWOUT", True, _flag),        # 1..4-output heads: tap-major GEMM + shifted sum
+    ("use_conv_strip", "P2P_CONV_STRIP", True, _flag),          # up6 (32 <-> 128 channels): LDS strip, weights in registers
+    ("use_conv_fewin", "P2P_CONV_FEWIN", True, _flag),          # 8-channel inputs: weights in registers, strip in LDS
+    ("wgemm_want", "P2P_WGEMM_WANT", 512, int),                 # workgroups wanted per 128x128-tile weight-gradient GEMM
+    # f32 (parity) mode is BATCH-INVARIANT on the data path: every per-image result (activations, data gradients) is produced
+    # by the same kernel variant, the same K split and the same statistics algorithm whatever the batch size, so an N-rank
+    # sharded step equals the 1-rank step image by image, bit for bit, and differs only in the order of the final weight-
+    # gradient sums.  (The heuristics otherwise look at the batch: a 2+2 split of a batch of 4 then rounds differently,
+    # and one ReLU flip in the 1x1 .. 4x4 layers is enough to move Adam's first steps apart -- tests/test_dp_gpu.py.)
+    # (__init__ turns it off for bf16)
+    ("batch_invariant", "P2P_BATCH_INVARIANT", True, _flag),
+    ("wgemm_pipe", "P2P_WGEMM_PIPE", True, _flag),
+    ("wgemm_want_pipe", "P2P_WGEMM_WANT_PIPE", 256, int),
+    # workgroups wanted per implicit-GEMM launch; 0 = by batch (_splitk): every extra K slice is another f32 slab that the
+    # layer's consumers (normalisation forward / backward) read, which is what a launch-bound small batch pays for
+    ("splitk_target", "P2P_SPLITK_TARGET", 0, int),
+    # partial-pixel stores (the source channels of the last concat buffer, the halves of the discriminator's fake pixel) are
+    # issued by the kernel that writes the rest of the pixel (0: separate stores in p2p_pack_pair, the r02 form)
+    ("full_pixels", "P2P_FULL_PIXELS", True, _flag),
+    ("fuse_act_bwd", "P2P_FUSE_ACT_BWD", 1, int),               # D.last data gradient + LeakyReLU backward in one launch
+    # Adam emitting the operand copies of the weights it updates (one pass, p2p_adam_prep_batched): measured 0.198 ms against
+    # 0.187 ms for the flat Adam + batched copy launch on c2 (the tiled kernel streams slower than the flat one): off
+    ("fuse_adam", None, False, None),       # (no environment switch: tests/test_train_step_gpu.py toggles the attribute)
+    ("use_head_fused", "P2P_HEAD_FUSED", True, _flag),          # indexed head: conv + softmax + CCE + argmax + gradient in one launch
+    ("split_prep", "P2P_SPLIT_PREP", 1, int),                   # weight copies of the early-Adam part refreshed right behind it
+    # forks that follow p2p_norm_act_bwd / p2p_act_bwd ride on that kernel's own completion signal (p2p_arm_stop_event) instead of
+    # a marker packet on the main stream; 0 = every fork is an event record
+    ("side.stop_event_forks", "P2P_STOP_EVENT_FORKS", True, _flag),
+)
+# GATES decide whether a step is recorded, replayed or elided at all, not which kernels a recorded step holds.
+GATES = (
+    # replay of the recorded step through ONE library call (see _REC below), at every batch size
+    ("replay_max_batch", "P2P_REPLAY_MAX_BATCH", 1 << 30, int),
+    ("replay_enabled", "P2P_REPLAY", True, _flag),
+    # The encoder block whose output map is 1x1 under InstanceNorm (the sixth at 64x64; none from 128x128 on): over one pixel
+    # x - mean(x) is exactly 0, so its output is act(beta) whatever its convolution computes, d(raw) is exactly 0, and with it
+    # its kernel's and gamma's gradients and the data gradient it hands to the block above; Adam never moves the kernel
+    # (DESIGN.md section 4).  The fused train steps leave that work out: 0 = issue everything; 1 = no forward / data-gradient
+    # / weight-gradient GEMM of the block and its kernel out of the in-step weight-copy launch, with the entry points and the
+    # launch count per entry point the step has always had (the normalisation runs on a zero "convolution result", Adam
+    # still passes over the kernel and leaves it as it is); 2 = also the 1x1 normalisation kernels that read no convolution
+    # result (p2p_norm_act_fwd_1x1 / _bwd_1x1) and Adam with a hole (p2p_adam_flat_dev_excl).  Bit-identical results at
+    # every level (tests/test_dead_bottleneck_gpu.py).  The level in force enters the replay key as _elide.
+    ("elide_dead_bottleneck", "P2P_ELIDE_DEAD", 1, int),
+)
+
+
+_SWITCH_VALUES = operator.attrgetter(*(attr for attr, *_ in SWITCHES))     # engine -> the switch part of its replay key
+
+
+def _switch_holder(eng, attr):
+    """(object, attribute name) of a table entry"""
+    *path, name = attr.split(".")
+    for p in path:
+        eng = getattr(eng, p)
+    return eng, name
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -69,66 +133,6 @@ def _op(name, *args):
         raise L.P2PError(f"{name} failed: " + L.lib().p2p_last_error().decode())
     if _REC[0] is not None:
         _REC[0].append((name, args))
-
-
-class ReplayCall(C.Structure):
-    """include/p2pgan.h p2p_replay_call"""
-    MAX_ARGS = 24
-    _fields_ = [("fn", C.c_int), ("nargs", C.c_int), ("ind64", C.c_uint), ("ind32", C.c_uint), ("a", C.c_ulonglong * 24)]
-
-
-_M64 = (1 << 64) - 1
-_F32 = __import__("struct").Struct("<f")
-_U32 = __import__("struct").Struct("<I")
-
-
-def _pack_arg(argtype, v):
-    """one recorded ctypes argument as (8-byte slot, indirection width): what ctypes would hand to the entry point.  A ctypes
-    scalar OBJECT (c_void_p / c_float / c_longlong instance) is read when the call is issued, exactly as ctypes does -- the
-    engine's batch, result and hyper-parameter slots rely on that -- so it is packed as the object's address."""
-    if isinstance(v, C._SimpleCData):
-        width = C.sizeof(v)
-        if width not in (4, 8):
-            raise TypeError(f"cannot replay a {type(v).__name__} argument")
-        return C.addressof(v), width
-    if argtype is C.c_float:
-        return _U32.unpack(_F32.pack(v))[0], 0
-    if argtype in (C.c_int, C.c_longlong):
-        return int(v) & _M64, 0
-    # pointers: void* and pointers to structures
-    if v is None:
-        return 0, 0
-    if isinstance(v, int):
-        return v & _M64, 0
-    if isinstance(v, (C.Structure, C.Array)):
-        return C.addressof(v), 0
-    obj = getattr(v, "_obj", None)          # C.byref(x)
-    if obj is not None:
-        return C.addressof(obj), 0
-    raise TypeError(f"cannot replay an argument of type {type(v).__name__}")
-
-
-def pack_replay(rec):
-    """list of (entry point name, ctypes arguments) -> (array of p2p_replay_call, n).  The caller keeps `rec` alive: the records
-    hold the addresses of the ctypes objects inside it."""
-    lib = L.lib()
-    arr = (ReplayCall * len(rec))()
-    for k, (name, args) in enumerate(rec):
-        types = L.SIGNATURES[name]
-        fn = lib.p2p_replay_fn_index(name.encode())
-        if fn < 0 or len(args) != len(types) or lib.p2p_replay_fn_nargs(fn) != len(types):
-            raise L.P2PError(f"{name} with {len(args)} arguments is not replayable")
-        c = arr[k]
-        c.fn, c.nargs = fn, len(args)
-        i64 = i32 = 0
-        for j, (t, v) in enumerate(zip(types, args)):
-            c.a[j], ind = _pack_arg(t, v)
-            if ind == 8:
-                i64 |= 1 << j
-            elif ind == 4:
-                i32 |= 1 << j
-        c.ind64, c.ind32 = i64, i32
-    return arr, len(rec)
 
 
 class _RecDP:
@@ -200,9 +204,7 @@ class _SideStream:
     def __init__(self, device, enabled):
         self.enabled = enabled and torch.device(device).type == "cuda"
         self.stream = torch.cuda.Stream(device=device) if self.enabled else None
-        # forks that follow p2p_norm_act_bwd / p2p_act_bwd ride on that kernel's own completion signal (p2p_arm_stop_event) instead of
-        # a marker packet on the main stream; 0 = every fork is an event record
-        self.stop_event_forks = os.environ.get("P2P_STOP_EVENT_FORKS", "1") != "0"
+        self.stop_event_forks = True        # (SWITCHES)
         self._pending = None
 
     def prefork(self):
@@ -261,192 +263,6 @@ class _NullCtx:
         return False
 
 
-class HaloBuf:
-    """NHWC activation buffer with a zero halo of HALO pixels around every image."""
-
-    def __init__(self, n, h, w, c, dtype, device):
-        self.n, self.h, self.w, self.c, self.dtype = n, h, w, c, dtype
-        self.hp, self.wp = h + 2 * HALO, w + 2 * HALO
-        # No kernel reads outside the pixels of a view any more (include/p2pgan.h, Conventions; round 1's wgemm tiles ran
-        # past short pixels); the 256 zeroed tail elements stay as a guard band.
-        numel = n * self.hp * self.wp * c
-        self._flat = torch.zeros(numel + 256, dtype=_torch_dtype(dtype), device=device)
-        self.t = self._flat[:numel].view(n, self.hp, self.wp, c)
-        self.esz = self.t.element_size()
-        self._views = {}
-
-    def view(self, coff=0, n0=0):
-        """p2p_tensor of the interior (channel offset `coff`, first image `n0`); the descriptors are cached -- a step asks for
-        ~200 of them and the buffers never move"""
-        v = self._views.get((coff, n0))
-        if v is None:
-            off = ((n0 * self.hp + HALO) * self.wp + HALO) * self.c + coff
-            v = self._views[(coff, n0)] = L.Tensor(self.t.data_ptr() + off * self.esz, self.hp * self.wp, self.wp, self.c)
-        return v
-
-
-class DenseBuf:
-    """Dense [N*H*W][C] tensor (conv raw outputs, gradient sources)."""
-
-    def __init__(self, n, h, w, c, torch_dtype, device):
-        self.n, self.h, self.w, self.c = n, h, w, c
-        self.t = torch.empty((n * h * w, c), dtype=torch_dtype, device=device)
-        self.esz = self.t.element_size()
-        self._views = {}
-
-    def view(self, coff=0, n0=0):
-        v = self._views.get((coff, n0))
-        if v is None:
-            v = self._views[(coff, n0)] = L.Tensor(self.t.data_ptr() + (n0 * self.h * self.w * self.c + coff) * self.esz,
-                                                   self.h * self.w, self.w, self.c)
-        return v
-
-    def ptr(self, n0=0):
-        return C.c_void_p(self.t.data_ptr() + n0 * self.h * self.w * self.c * self.esz)
-
-    def gsrc(self, coff=0, kind=1, nslabs=1, n0=0):
-        return L.GSrc(self.t.data_ptr() + n0 * self.h * self.w * self.c * self.esz, kind, nslabs,
-                      self.n * self.h * self.w * self.c, self.c, coff)
-
-
-def pad8(c):
-    """channel count padded so that a pixel is a whole number of 16-byte chunks (bf16 and f32 alike)"""
-    return (c + 7) // 8 * 8
-
-
-def up32(c):
-    return (c + 31) // 32 * 32
-
-
-def _p(t, off_elems=0):
-    return C.c_void_p(t.data_ptr() + off_elems * t.element_size())
-
-
-NULL = C.c_void_p(0)
-
-
-class ParamStore:
-    """Flat f32 parameter / gradient / Adam-moment buffers with named views.
-
-    `shapes` keeps the Keras variable order (names, export, iteration).  The MEMORY order is chosen for the data-parallel
-    all-reduce: conv kernels first, in the order their gradients complete in the backward pass (head, up6..up1,
-    down6..down1), then every small tensor (gamma/beta/bias) in one tail region.  Contiguous runs of kernels form the
-    gradient buckets that are all-reduced while the backward pass is still running; the tail region goes last.
-    Every tensor is 16-byte aligned."""
-
-    BUCKET_MIN = 4 * 1024 * 1024      # floats (16 MB): a bucket closes once it holds at least this much
-
-    def __init__(self, shapes, device):
-        self.shapes = OrderedDict(shapes)
-        self.offsets = OrderedDict()
-        kernels = [k for k in self.shapes if k.endswith(".kernel")]
-        small = [k for k in self.shapes if not k.endswith(".kernel")]
-        off, self.buckets, start, self.bucket_of = 0, [], 0, {}
-        for k in reversed(kernels):           # backward completion order
-            self.offsets[k] = off
-            off += int(np.prod(self.shapes[k]))
-            off = (off + 3) // 4 * 4
-            self.bucket_of[k[:-7]] = len(self.buckets)
-            if off - start >= self.BUCKET_MIN:
-                self.buckets.append((start, off))
-                start = off
-        if off > start:
-            self.buckets.append((start, off))
-        self.bucket_last_layer = {}           # bucket index -> layer whose gradient completes it
-        for k in reversed(kernels):
-            self.bucket_last_layer[self.bucket_of[k[:-7]]] = k[:-7]
-        self.small_range = (off, off)
-        for k in small:
-            self.offsets[k] = off
-            off += int(np.prod(self.shapes[k]))
-            off = (off + 3) // 4 * 4
-        self.small_range = (self.small_range[0], off)
-        self.numel = off
-        self.params = torch.zeros(off, dtype=torch.float32, device=device)
-        self.grads = None                     # attached by the engine (one allocation for both networks + loss slots)
-        self.m = torch.zeros(off, dtype=torch.float32, device=device)
-        self.v = torch.zeros(off, dtype=torch.float32, device=device)
-        self.t = 0                            # Adam iteration count (host mirror of t_dev)
-        self.t_dev = torch.zeros(1, dtype=torch.int32, device=device)       # device-resident: graph replay advances it
-        self.lr_t_dev = torch.zeros(1, dtype=torch.float32, device=device)
-
-    def count(self):
-        return int(sum(int(np.prod(s)) for s in self.shapes.values()))
-
-    def view(self, buf, name):
-        o = self.offsets[name]
-        return buf[o:o + int(np.prod(self.shapes[name]))].view(self.shapes[name])
-
-    def p(self, name):
-        return _p(self.params, self.offsets[name])
-
-    def g(self, name):
-        return _p(self.grads, self.offsets[name])
-
-    def variable_name(self, t):
-        """name of the variable whose view `t` is (an entry of trainable_variables), or None"""
-        if not isinstance(t, torch.Tensor) or t.device != self.params.device or t.dtype != torch.float32:
-            return None
-        off = t.data_ptr() - self.params.data_ptr()
-        if off < 0 or off % 4 or off >= 4 * self.numel:
-            return None
-        if getattr(self, "_by_offset", None) is None:
-            self._by_offset = {o: k for k, o in self.offsets.items()}
-        name = self._by_offset.get(off // 4)
-        return name if name is not None and tuple(t.shape) == tuple(self.shapes[name]) else None
-
-    def load(self, values):
-        for k in self.shapes:
-            self.view(self.params, k).copy_(torch.as_tensor(np.asarray(values[k]), dtype=torch.float32))
-
-    def export(self, buf=None):
-        buf = self.params if buf is None else buf
-        return OrderedDict((k, self.view(buf, k).detach().cpu().numpy().copy()) for k in self.shapes)
-
-
-def generator_param_shapes(in_ch, out_ch):
-    """Variable order / shapes of UnetGenerator (networks.py:53-98); conv kernels keep the Keras layouts
-    HWIO (Conv2D) and (kh,kw,Cout,Cin) (Conv2DTranspose) == [tap][Cg][Cd] in both cases."""
-    shapes = OrderedDict()
-    c = in_ch
-    for i, f in enumerate(DOWN_FILTERS, start=1):
-        shapes[f"down{i}.kernel"] = (4, 4, c, f)
-        if i > 1:
-            shapes[f"down{i}.gamma"] = (f,)
-            shapes[f"down{i}.beta"] = (f,)
-        c = f
-    skips = list(reversed(DOWN_FILTERS[:-1])) + [in_ch]
-    for i, (f, s) in enumerate(zip(UP_FILTERS, skips), start=1):
-        shapes[f"up{i}.kernel"] = (4, 4, f, c)
-        shapes[f"up{i}.gamma"] = (f,)
-        shapes[f"up{i}.beta"] = (f,)
-        c = f + s
-    shapes["last.kernel"] = (4, 4, c, out_ch)
-    shapes["last.bias"] = (out_ch,)
-    return shapes
-
-
-def discriminator_param_shapes(in_ch):
-    """PatchDiscriminator variables (networks.py:39-50)."""
-    return OrderedDict([("down.kernel", (4, 4, 2 * in_ch, 64)), ("last.kernel", (4, 4, 64, 1)), ("last.bias", (1,))])
-
-
-class LayerW:
-    """Per-layer weight copies in the activation dtype, derived from the f32 master W[16][Cg][Cd] after every
-    Adam step (p2p_weight_prep_pad):
-      wt [16][up32(Cd)][hi_pad]  B operand of op G (conv forward / convT dgrad), contraction over the gathered
-                                 hi view whose pixels hold hi_pad channels in HBM;
-      wn [16][up32(Cg)][lo_pad]  B operand of op P (convT forward / conv dgrad), contraction over the lo view;
-      wd [16][Cg][Cd]            unpadded copy, only for the direct (non-MFMA) cross-check kernels.
-    Rows/columns beyond the real [Cg][Cd] block are zero."""
-
-    def __init__(self, cg, cd, hi_pad, lo_pad, need_g, need_p):
-        self.cg, self.cd, self.hi_pad, self.lo_pad = cg, cd, hi_pad, lo_pad
-        self.need_g, self.need_p = need_g, need_p
-        self.wt = self.wn = self.wd = None
-        self.main = cg % 32 == 0 and cd % 32 == 0 and hi_pad == cg and lo_pad == cd
-
-
 class Pix2PixEngine:
     """One generator + one discriminator + their optimizers on one GPU."""
 
@@ -499,22 +315,12 @@ class Pix2PixEngine:
         self.side_hist = _SideStream(self.device, overlap_wgrad)     # third stream: histogram-loss chain
         self._dp = None             # parallel.DataParallel of the step in flight
         self._batch_offset = 0      # samples of the global batch in front of this rank's shard (keys the dropout stream)
-        self.use_conv_fewout = os.environ.get("P2P_CONV_FEWOUT", "1") != "0"    # 1..4-output heads: tap-major GEMM + shifted sum
-        self.use_conv_strip = os.environ.get("P2P_CONV_STRIP", "1") != "0"      # up6 (32 <-> 128 channels): LDS strip, weights in registers
-        self.use_conv_fewin = os.environ.get("P2P_CONV_FEWIN", "1") != "0"      # 8-channel inputs: weights in registers, strip in LDS
-        self.wgemm_want = int(os.environ.get("P2P_WGEMM_WANT", "512"))     # workgroups wanted per 128x128-tile weight-gradient GEMM
-        # f32 (parity) mode is BATCH-INVARIANT on the data path: every per-image result (activations, data gradients) is produced
-        # by the same kernel variant, the same K split and the same statistics algorithm whatever the batch size, so an N-rank
-        # sharded step equals the 1-rank step image by image, bit for bit, and differs only in the order of the final weight-
-        # gradient sums.  (The heuristics below otherwise look at the batch: a 2+2 split of a batch of 4 then rounds differently,
-        # and one ReLU flip in the 1x1 .. 4x4 layers is enough to move Adam's first steps apart -- tests/test_dp_gpu.py.)
-        self.batch_invariant = dtype == L.F32 and os.environ.get("P2P_BATCH_INVARIANT", "1") != "0"
-        self.wgemm_pipe = os.environ.get("P2P_WGEMM_PIPE", "1") != "0"
-        self.wgemm_want_pipe = int(os.environ.get("P2P_WGEMM_WANT_PIPE", "256"))
-        # workgroups wanted per implicit-GEMM launch; 0 = by batch (_splitk): every extra K slice is another f32 slab that the
-        # layer's consumers (normalisation forward / backward) read, which is what a launch-bound small batch pays for
-        self.splitk_target = int(os.environ.get("P2P_SPLITK_TARGET", "0"))
-        self._prep_table = {}
+        for attr, env, default, parse in SWITCHES + GATES:
+            text = os.environ.get(env) if env else None
+            obj, name = _switch_holder(self, attr)
+            setattr(obj, name, default if text is None else parse(text))
+        self.batch_invariant = self.batch_invariant and dtype == L.F32
+        self._prep_table, self._adam_tables = {}, {}
         self._head_prepped = False
         # tape calls (tape.py): arenas of activations per call, pooled by (network, images) once a tape is released; the
         # workspaces they share per image count; the op-P copy of G.down1, prepared only when a tape needs d(source)
@@ -522,37 +328,10 @@ class Pix2PixEngine:
         self._copies_version = 0
         self._down1_wn, self._down1_wn_key = None, None
         self.tape_refusal = None        # set by a model whose configuration has no tape path (data parallelism)
-        # partial-pixel stores (the source channels of the last concat buffer, the halves of the discriminator's fake pixel) are
-        # issued by the kernel that writes the rest of the pixel (0: separate stores in p2p_pack_pair, the r02 form)
-        self.full_pixels = os.environ.get("P2P_FULL_PIXELS", "1") != "0"
-        self.fuse_act_bwd = int(os.environ.get("P2P_FUSE_ACT_BWD", "1"))   # D.last data gradient + LeakyReLU backward in one launch
-        # Adam emitting the operand copies of the weights it updates (one pass, p2p_adam_prep_batched): measured 0.198 ms against
-        # 0.187 ms for the flat Adam + batched copy launch on c2 (the tiled kernel streams slower than the flat one): off
-        self.fuse_adam = False      # (no environment switch: tests/test_train_step_gpu.py toggles the attribute)
-        self._adam_tables = {}
-        # replay of the recorded step through ONE library call (see _REC above), at every batch size
-        self.replay_max_batch = int(os.environ.get("P2P_REPLAY_MAX_BATCH", str(1 << 30)))
         self._replays, self._replay_seen = OrderedDict(), {}
         self._replay_fn = L.lib().p2p_replay
-        self.replay_enabled = os.environ.get("P2P_REPLAY", "1") != "0"
         self._slot_src, self._slot_real, self._slot_out = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._real_view = L.Tensor(None, 0, 0, 4)
-        self.use_head_fused = os.environ.get("P2P_HEAD_FUSED", "1") != "0"    # indexed head: conv + softmax + CCE + argmax + gradient in one launch
-        # histogram loss: three shared kernel rows per pixel with all components in one workgroup (forward and backward), the real
-        # image contracted over its distinct colours.  The per-component kernels remain in the library as cross-checks
-        # (tests/test_hist_indexed_gpu.py calls them directly); the engine has one path
-        self.hist_fwd3 = self.hist_bwd3 = self.hist_points = 1
-        self.split_prep = int(os.environ.get("P2P_SPLIT_PREP", "1"))    # weight copies of the early-Adam part refreshed right behind it
-        # The encoder block whose output map is 1x1 under InstanceNorm (the sixth at 64x64; none from 128x128 on): over one pixel
-        # x - mean(x) is exactly 0, so its output is act(beta) whatever its convolution computes, d(raw) is exactly 0, and with it
-        # its kernel's and gamma's gradients and the data gradient it hands to the block above; Adam never moves the kernel
-        # (DESIGN.md section 4).  The fused train steps leave that work out: 0 = issue everything; 1 = no forward / data-gradient
-        # / weight-gradient GEMM of the block and its kernel out of the in-step weight-copy launch, with the entry points and the
-        # launch count per entry point the step has always had (the normalisation runs on a zero "convolution result", Adam
-        # still passes over the kernel and leaves it as it is); 2 = also the 1x1 normalisation kernels that read no convolution
-        # result (p2p_norm_act_fwd_1x1 / _bwd_1x1) and Adam with a hole (p2p_adam_flat_dev_excl).  Bit-identical results at
-        # every level (tests/test_dead_bottleneck_gpu.py).
-        self.elide_dead_bottleneck = int(os.environ.get("P2P_ELIDE_DEAD", "1"))
         self._dead = next((i for i in range(2, len(DOWN_FILTERS) + 1) if img_size // 2 ** i == 1), None)
         self._frozen = None             # element range of the dead block's kernel in the generator's flat buffers
         if self._dead is not None:
@@ -617,33 +396,28 @@ class Pix2PixEngine:
                     lw.wd = torch.zeros(16 * cg * cd, dtype=tdt, device=dev)
                 self.W[(sid, name)] = lw
 
-    def _prep_tasks(self, part="all", live=False):
-        """Device table of p2p_prep_task descriptors (one per weight copy set); the pointers are stable for the life
-        of the engine, so it is built once.  part = "head": the generator layers whose parameters lie in front of the last
-        gradient bucket (what _adam_head updates early), "rest": the others, "all": every layer, "G" / "D": one network's
-        layers (the per-network optimizer step, apply_adam_store).  live: without the dead bottleneck's kernel (its master does
-        not move inside a fused step; every outside writer refreshes the complete table)."""
-        want = part
-        if live:
-            part = (part, "live")           # (the cache key from here on)
-        if self._prep_table.get(part) is not None:
-            return self._prep_table[part]
+    def _in_head(self, sid, name):
+        """the layer's kernel lies in front of the last gradient bucket: what _adam_head updates early"""
+        lw = self.W[(sid, name)]
         head_end = self.G.buckets[-1][0] if len(self.G.buckets) >= 2 else 0
-        specs = []
-        for (sid, name), lw in self.W.items():
-            in_head = sid == "G" and self.G.offsets[name + ".kernel"] + 16 * lw.cg * lw.cd <= head_end
-            if (want == "head" and not in_head) or (want == "rest" and in_head) or (want in ("G", "D") and sid != want):
-                continue
-            if live and (sid, name) == ("G", f"down{self._dead}"):
-                continue
-            master = self._store(sid).p(name + ".kernel")
-            if lw.wt is not None or lw.wn is not None:
-                specs.append((master, lw.cg, lw.cd, lw.wn, up32(lw.cg), lw.lo_pad, lw.wt, up32(lw.cd), lw.hi_pad))
-            if lw.wd is not None:
-                specs.append((master, lw.cg, lw.cd, lw.wd, lw.cg, lw.cd, None, 0, 0))
+        return sid == "G" and self.G.offsets[name + ".kernel"] + 16 * lw.cg * lw.cd <= head_end
+
+    def _copy_sets(self, sid, name):
+        """a layer's weight copy sets (master, cg, cd, wn, wn rows, wn columns, wt, wt rows, wt columns): the padded operand pair
+        of the MFMA kernels, then the unpadded copy of the direct kernels"""
+        lw = self.W[(sid, name)]
+        master = self._store(sid).p(name + ".kernel")
+        sets = []
+        if lw.wt is not None or lw.wn is not None:
+            sets.append((master, lw.cg, lw.cd, lw.wn, up32(lw.cg), lw.lo_pad, lw.wt, up32(lw.cd), lw.hi_pad))
+        if lw.wd is not None:
+            sets.append((master, lw.cg, lw.cd, lw.wd, lw.cg, lw.cd, None, 0, 0))
+        return sets
+
+    def _task_table(self, specs):
+        """copy sets -> device table of p2p_prep_task descriptors (raw bytes, ntasks, total blocks)"""
         if not specs:
-            self._prep_table[part] = (None, 0, 0)
-            return self._prep_table[part]
+            return None, 0, 0
         tasks = (L.PrepTask * len(specs))()
         first = 0
         for k, (master, cg, cd, wn, wn_r, wn_c, wt, wt_r, wt_c) in enumerate(specs):
@@ -657,9 +431,26 @@ class Pix2PixEngine:
             t.Cg, t.Cd, t.wn_rows, t.wn_cols, t.wt_rows, t.wt_cols = cg, cd, wn_r, wn_c, wt_r, wt_c
             t.tiles_g, t.tiles_d, t.first_block = tg.value, td.value, first
             first += nb
-        raw = torch.frombuffer(bytearray(bytes(tasks)), dtype=torch.uint8).to(self.device)
-        self._prep_table[part] = (raw, len(specs), first)
-        return self._prep_table[part]
+        return torch.frombuffer(bytearray(bytes(tasks)), dtype=torch.uint8).to(self.device), len(specs), first
+
+    def _prep_tasks(self, part="all", live=False):
+        """Device table of p2p_prep_task descriptors (one per weight copy set); the pointers are stable for the life
+        of the engine, so it is built once.  part = "head": the generator layers whose parameters lie in front of the last
+        gradient bucket (what _adam_head updates early), "rest": the others, "all": every layer, "G" / "D": one network's
+        layers (the per-network optimizer step, apply_adam_store).  live: without the dead bottleneck's kernel (its master does
+        not move inside a fused step; every outside writer refreshes the complete table)."""
+        key = (part, "live") if live else part
+        if self._prep_table.get(key) is None:
+            specs = []
+            for sid, name in self.W:
+                in_head = self._in_head(sid, name)
+                if (part == "head" and not in_head) or (part == "rest" and in_head) or (part in ("G", "D") and sid != part):
+                    continue
+                if live and (sid, name) == ("G", f"down{self._dead}"):
+                    continue
+                specs += self._copy_sets(sid, name)
+            self._prep_table[key] = self._task_table(specs)
+        return self._prep_table[key]
 
     def _adam_table(self, part):
         """Device task table of p2p_adam_prep_batched for one part of the parameters -- "G_head": the generator kernels in front
@@ -667,45 +458,18 @@ class Pix2PixEngine:
         discriminator's kernels -- each kernel listed ONCE with its first copy set; "extra": the remaining copy sets (the
         unpadded copies of the edge layers), refreshed by a plain p2p_weight_prep_batched afterwards.
         Returns (table tensor, ntasks, total blocks, elements)."""
-        if part in self._adam_tables:
-            return self._adam_tables[part]
-        head_end = self.G.buckets[-1][0] if len(self.G.buckets) >= 2 else 0
-        specs, n_elems = [], 0
-        for (sid, name), lw in self.W.items():
-            store = self._store(sid)
-            in_head = sid == "G" and store.offsets[name + ".kernel"] + 16 * lw.cg * lw.cd <= head_end
-            where = "D" if sid == "D" else ("G_head" if in_head else "G_rest")
-            master = store.p(name + ".kernel")
-            sets = []
-            if lw.wt is not None or lw.wn is not None:
-                sets.append((master, lw.cg, lw.cd, lw.wn, up32(lw.cg), lw.lo_pad, lw.wt, up32(lw.cd), lw.hi_pad))
-            if lw.wd is not None:
-                sets.append((master, lw.cg, lw.cd, lw.wd, lw.cg, lw.cd, None, 0, 0))
-            if not sets:        # a kernel without copies still has to be updated: a task that writes none
-                sets.append((master, lw.cg, lw.cd, None, 0, 0, None, 0, 0))
-            if part == where:
-                specs.append(sets[0])
-                n_elems += 16 * lw.cg * lw.cd
-            elif part == "extra":
-                specs += sets[1:]
-        if not specs:
-            self._adam_tables[part] = (None, 0, 0, 0)
-            return self._adam_tables[part]
-        tasks = (L.PrepTask * len(specs))()
-        first = 0
-        for k, (master, cg, cd, wn, wn_r, wn_c, wt, wt_r, wt_c) in enumerate(specs):
-            tg, td = C.c_int(0), C.c_int(0)
-            nb = L.lib().p2p_weight_prep_task_blocks(cg, cd, wn_r, wn_c, wt_r, wt_c, int(wn is not None), int(wt is not None),
-                                                     C.byref(tg), C.byref(td))
-            t = tasks[k]
-            t.w = master.value
-            t.wn = wn.data_ptr() if wn is not None else None
-            t.wt = wt.data_ptr() if wt is not None else None
-            t.Cg, t.Cd, t.wn_rows, t.wn_cols, t.wt_rows, t.wt_cols = cg, cd, wn_r, wn_c, wt_r, wt_c
-            t.tiles_g, t.tiles_d, t.first_block = tg.value, td.value, first
-            first += nb
-        raw = torch.frombuffer(bytearray(bytes(tasks)), dtype=torch.uint8).to(self.device)
-        self._adam_tables[part] = (raw, len(specs), first, n_elems)
+        if part not in self._adam_tables:
+            specs, n_elems = [], 0
+            for (sid, name), lw in self.W.items():
+                where = "D" if sid == "D" else ("G_head" if self._in_head(sid, name) else "G_rest")
+                # (a kernel without copies still has to be updated: a task that writes none)
+                sets = self._copy_sets(sid, name) or [(self._store(sid).p(name + ".kernel"), lw.cg, lw.cd, None, 0, 0, None, 0, 0)]
+                if part == where:
+                    specs.append(sets[0])
+                    n_elems += 16 * lw.cg * lw.cd
+                elif part == "extra":
+                    specs += sets[1:]
+            self._adam_tables[part] = self._task_table(specs) + (n_elems,)
         return self._adam_tables[part]
 
     def _adam_prep(self, part):
@@ -1181,16 +945,13 @@ class Pix2PixEngine:
         if (masks is not None or not apply_update or B > self.replay_max_batch or self.device.type != "cuda"
                 or L.call is not _ORIG_CALL or not self.replay_enabled or torch.cuda.is_current_stream_capturing()):
             return None
-        # everything the recorded calls hold BY VALUE: the switches that choose kernels, the K-split / grid targets and the stream
+        # everything the recorded calls hold BY VALUE: the switches that choose kernels and K-split / grid targets (SWITCHES) and the stream
         # the step was issued on (raw handle inside the records -- the id of the torch stream object rides along, so a recycled
         # handle value of a NEW stream does not match an old recording).  Adam's hyper-parameters and the dropout seed are NOT
         # part of the key: the records hold the address of their slots (_slot_lr ...), one recording serves every value.
         st = torch.cuda.current_stream()
-        return (kind, B, self.side.enabled, self.side.stop_event_forks, self.side_hist.enabled, self.fuse_adam, self.use_head_fused, self.hist_fwd3, self.hist_bwd3,
-                self.hist_points, self.fuse_act_bwd, self.split_prep, self.full_pixels, self.use_conv_fewout, self.use_conv_strip, self.use_conv_fewin,
-                self.use_mfma, bool(self.batch_invariant), bool(self.wgemm_pipe), int(self.splitk_target), int(self.wgemm_want), int(self.wgemm_want_pipe),
-                int(st.cuda_stream), int(st.stream_id), int(self._elide),
-                None if dp is None else id(dp)) + extra
+        return (kind, B, _SWITCH_VALUES(self), self.use_mfma, self.side.enabled, self.side_hist.enabled,
+                int(st.cuda_stream), int(st.stream_id), int(self._elide), None if dp is None else id(dp)) + extra
 
     def _bind_batch(self, src_t, real_t):
         """the batch tensors of this step behind the re-usable pointer slots the recorded calls hold"""
@@ -1381,29 +1142,21 @@ class Pix2PixEngine:
                C.byref(out_view), self._wn("D", "last"), C.byref(act_view), LEAKY_ALPHA, _stream())
         return True
 
-    # ------------------------------------------------------------------ train step (RGBA models)
-    def train_step_rgba(self, source, real, lambda_l1, lambda_hist=None, masks=None, global_batch=None,
-                        apply_update=True, dp=None, batch_offset=0):
-        """Pix2PixModel.train_step / Pix2PixHistogramModel (pix2pix_model.py:62-89,242-250).
-        Returns a device tensor [g_total, g_adv, g_l1, g_hist, d_total, d_real, d_fake] (f32)."""
-        B = int(source.shape[0])
-        P = self.plan(B)
-        S, ic = self.S, self.in_ch
-        Bg = global_batch or B
-        self._dp = dp
-        self._batch_offset = int(batch_offset)
-        src_t, real_t = self._to_device(source, ic, B), self._to_device(real, ic, B)
+    def _run_step(self, kind, key_extra, P, src_t, real_t, body, masks, apply_update, hist=False):
+        """One fused train step of the communicator in self._dp: replayed where a recording with its key exists, else body() is
+        issued, and recorded the second time the key is seen.  The one place that puts the elision level in force and that wraps
+        the communicator of a step being recorded (_RecDP): the bodies read self._dp."""
+        dp = self._dp
         self._elide = self._elision()
         try:
-            key = self._replay_key("rgba", B, masks, dp, apply_update, float(lambda_l1),
-                                   None if lambda_hist is None else float(lambda_hist), Bg, int(batch_offset))
+            key = self._replay_key(kind, P["B"], masks, dp, apply_update, *key_extra)
             if key in self._replays:
-                return self._replay(key, P, src_t, real_t, hist=lambda_hist is not None)
+                return self._replay(key, P, src_t, real_t, hist=hist)
             recording = self._begin_record(key)
             if recording and dp is not None:
-                dp = self._dp = _RecDP(dp)
+                self._dp = _RecDP(dp)
             try:
-                out = self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, dp)
+                out = body()
             except BaseException:
                 if recording:
                     self._end_record(key, False)
@@ -1414,7 +1167,22 @@ class Pix2PixEngine:
         finally:
             self._elide = 0         # every other path (hooked steps, tapes, generate) issues the whole network
 
-    def _train_step_rgba_body(self, P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, dp):
+    # ------------------------------------------------------------------ train step (RGBA models)
+    def train_step_rgba(self, source, real, lambda_l1, lambda_hist=None, masks=None, global_batch=None,
+                        apply_update=True, dp=None, batch_offset=0):
+        """Pix2PixModel.train_step / Pix2PixHistogramModel (pix2pix_model.py:62-89,242-250).
+        Returns a device tensor [g_total, g_adv, g_l1, g_hist, d_total, d_real, d_fake] (f32)."""
+        B = int(source.shape[0])
+        P = self.plan(B)
+        Bg = global_batch or B
+        self._dp, self._batch_offset = dp, int(batch_offset)
+        src_t, real_t = self._to_device(source, self.in_ch, B), self._to_device(real, self.in_ch, B)
+        key_extra = (float(lambda_l1), None if lambda_hist is None else float(lambda_hist), Bg, int(batch_offset))
+        return self._run_step("rgba", key_extra, P, src_t, real_t,
+                              lambda: self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update),
+                              masks, apply_update, hist=lambda_hist is not None)
+
+    def _train_step_rgba_body(self, P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update):
         S, ic = self.S, self.in_ch
         self._bind_batch(src_t, real_t)
         whole_fake = ic == 4 and self.src_ch == 8 and self.dcat_ch == 8 and self.full_pixels and self.out_ch == 4
@@ -1448,28 +1216,17 @@ class Pix2PixEngine:
             # concurrently with the discriminator forward/backward, and are joined before the tanh backward
             self.side_hist.fork()
             with self.side_hist.run():
-                g_extra = self._histogram_loss(P, B, Bg, lambda_hist, dp.allreduce_scalar_sum if dp is not None else None)
+                g_extra = self._histogram_loss(P, B, Bg, lambda_hist, self._dp.allreduce_scalar_sum if self._dp is not None else None)
         self.discriminator_forward(P, 2 * B)
-        h2 = S // 2
-        inv_bce = 1.0 / (Bg * h2 * h2)
-        # (dld / dlg are 8-channel pixels [g | padding]: whole-pixel stores with the switch on)
-        L.call("p2p_bce_logits_pad8" if self.full_pixels else "p2p_bce_logits", self.dtype, 2 * B, B, h2, h2,
-               C.byref(P["logits"].view()), inv_bce, C.byref(P["dld"].view()), C.byref(P["dlg"].view()), _p(self.loss_part), _stream())
+        self._bce_logits(P, B, Bg, P["dlg"].view())
         P["skip_g_through_d"] = False
         P["head_dbias_done"] = False
         self.discriminator_backward(P, B)
         if lambda_hist is not None:
             self.side_hist.join()
-        if self.full_pixels and self.out_ch == 4 and self.dz_ch == 8:
-            L.call("p2p_tanh_l1_bwd_pad8", self.dtype, B, S, S, C.byref(fake_view), C.byref(real_view),
-                   C.byref(P["g_dcat"].gsrc()), C.byref(g_extra) if g_extra is not None else None,
-                   float(lambda_l1) * inv_l1, C.byref(P["dz"].view()), _stream())
-        else:
-            L.call("p2p_tanh_l1_bwd", self.dtype, B, S, S, self.out_ch, C.byref(fake_view), C.byref(real_view),
-                   C.byref(P["g_dcat"].gsrc()), C.byref(g_extra) if g_extra is not None else None,
-                   float(lambda_l1) * inv_l1, C.byref(P["dz"].view()), _stream())
+        self._tanh_l1_bwd(P, fake_view, real_view, P["g_dcat"].gsrc(), g_extra, float(lambda_l1) * inv_l1)
         self.generator_backward(P)
-        return self._finish_step(P, lambda_l1, lambda_hist, apply_update)
+        return self._finish_step(4, self._finish_args(lambda_l1, lambda_hist), apply_update)
 
     def train_step_rgba_hooked(self, source, real, generator_loss, discriminator_loss, masks=None, apply_update=True):
         """train_step (pix2pix_model.py:62-89) for a subclass that OVERRIDES the loss hooks (pix2pix_model.py:44-56,242-250 are the
@@ -1484,7 +1241,7 @@ class Pix2PixEngine:
         kernels; single GPU, not replayed (the hooks are host code)."""
         B = int(source.shape[0])
         P = self.plan(B)
-        S, ic, h2 = self.S, self.in_ch, self.S // 2
+        S, ic = self.S, self.in_ch
         assert self.head == "tanh", "the palette-index model has a train_step of its own"
         self._dp, self._batch_offset = None, 0
         src_t, real_t = self._to_device(source, ic, B), self._to_device(real, ic, B)
@@ -1501,19 +1258,13 @@ class Pix2PixEngine:
         L.call("p2p_tanh_l1_fwd", self.dtype, B, S, S, self.out_ch, C.byref(P["z"].view()), C.byref(real_view), C.byref(fake_view), 0.0,
                _p(self.loss_part, 4 * 256), _p(fake32), _stream())
         self.discriminator_forward(P, 2 * B)
-        logits = P["logits"].t.detach().float().view(2 * B, h2, h2, 1)
-        lg_d = logits.clone().requires_grad_(True)
-        d_loss = discriminator_loss(lg_d[:B], lg_d[B:])
-        d_loss[0].backward()
-        lg_g = logits[B:].clone().requires_grad_(True)
+        d_loss, lg_d, lg_g = self._hook_discriminator(P, B, discriminator_loss)
         fake = fake32.view(B, S, S, self.out_ch).clone().requires_grad_(True)
         g_loss = generator_loss(lg_g, fake, real_t)
         g_loss[0].backward()
-        zero = lambda t: torch.zeros_like(t) if t.grad is None else t.grad          # noqa: E731  (a hook may ignore an input)
-        inner = slice(HALO, HALO + h2)
-        P["dld"].t[:, inner, inner, 0] = zero(lg_d).view(2 * B, h2, h2).to(self.tdt)      # pixels [g | 7 padding channels]
-        P["dlg"].t[:, inner, inner, 0] = zero(lg_g).view(B, h2, h2).to(self.tdt)
-        d_fake = zero(fake).contiguous()
+        self._write_dlogits(P["dld"], lg_d)
+        self._write_dlogits(P["dlg"], lg_g)
+        d_fake = (torch.zeros_like(fake) if fake.grad is None else fake.grad).contiguous()      # (a hook may ignore an input)
         P["hook_keep"] = (d_fake, lg_d, lg_g, fake)
         g_extra = L.GSrc(d_fake.data_ptr(), 2, 1, B * S * S * self.out_ch, self.out_ch, 0)
         P["skip_g_through_d"] = False
@@ -1522,14 +1273,50 @@ class Pix2PixEngine:
         L.call("p2p_tanh_l1_bwd", self.dtype, B, S, S, self.out_ch, C.byref(fake_view), C.byref(real_view), C.byref(P["g_dcat"].gsrc()),
                C.byref(g_extra), 0.0, C.byref(P["dz"].view()), _stream())
         self.generator_backward(P)
-        head = self._adam_head(apply_update)
-        self.side.join()
-        if apply_update:
-            self.apply_adam(g_from=head)
+        self._optimizer_tail(apply_update)
+        return self._hooked_result(g_loss, d_loss)
+
+    def _hook_discriminator(self, P, B, discriminator_loss):
+        """The discriminator's loss hook of a hooked step on an f32 copy of the logits, differentiated.  Returns (d_loss, the leaf
+        that carries d(loss)/d(logits), a leaf of its own with the fake half's logits for the generator's hook)."""
+        h2 = self.S // 2
+        logits = P["logits"].t.detach().float().view(2 * B, h2, h2, 1)
+        lg_d = logits.clone().requires_grad_(True)
+        d_loss = discriminator_loss(lg_d[:B], lg_d[B:])
+        d_loss[0].backward()
+        return d_loss, lg_d, logits[B:].clone().requires_grad_(True)
+
+    def _write_dlogits(self, buf, lg):
+        """the gradient a hook left on the logits `lg` (zero: a hook may ignore an input) into channel 0 of dld / dlg: pixels
+        [g | 7 padding channels]"""
+        inner = slice(HALO, HALO + self.S // 2)
+        g = torch.zeros_like(lg) if lg.grad is None else lg.grad
+        buf.t[:, inner, inner, 0] = g.view(lg.shape[:3]).to(self.tdt)
+
+    def _hooked_result(self, g_loss, d_loss):
         self.step_count += 1
         vals = [g_loss[0], g_loss[1], g_loss[2], g_loss[3] if len(g_loss) > 3 else torch.zeros((), device=self.device),
                 d_loss[0], d_loss[1], d_loss[2]]
         return torch.stack([v.detach().reshape(()).float() for v in vals])
+
+    def _tanh_l1_bwd(self, P, fake_view, real_view, gsrc, extra, scale):
+        """d(tanh head) into dz from the L1 term (scale), the adversarial gradient source and one more source: dz's 8-channel
+        pixels [g | padding] are stored whole with full_pixels on"""
+        B, S = P["B"], self.S
+        args = (C.byref(fake_view), C.byref(real_view), C.byref(gsrc) if gsrc is not None else None,
+                C.byref(extra) if extra is not None else None, scale, C.byref(P["dz"].view()), _stream())
+        if self.full_pixels and self.out_ch == 4 and self.dz_ch == 8:
+            L.call("p2p_tanh_l1_bwd_pad8", self.dtype, B, S, S, *args)
+        else:
+            L.call("p2p_tanh_l1_bwd", self.dtype, B, S, S, self.out_ch, *args)
+
+    def _bce_logits(self, P, B, Bg, dlg):
+        """the three BCE sums of the discriminator's logits and their gradients: dld (D's own loss) and, for the RGBA models, dlg
+        (the generator's adversarial term) -- 8-channel pixels [g | padding]: whole-pixel stores with full_pixels on"""
+        h2 = self.S // 2
+        L.call("p2p_bce_logits_pad8" if self.full_pixels else "p2p_bce_logits", self.dtype, 2 * B, B, h2, h2,
+               C.byref(P["logits"].view()), 1.0 / (Bg * h2 * h2), C.byref(P["dld"].view()), C.byref(dlg) if dlg is not None else None,
+               _p(self.loss_part), _stream())
 
     def generator_backward(self, P):
         """Backward of UnetGenerator from dz (the gradient at the head's pre-activation)."""
@@ -1615,16 +1402,32 @@ class Pix2PixEngine:
         dp.wait_all()
         self._dp = None
 
-    def _finish_step(self, P, lambda_l1, lambda_hist, apply_update):
+    def _optimizer_tail(self, apply_update, loss_rows=0):
+        """behind the backward pass of every train step: the early part of Adam, the weight-gradient stream joined, the loss
+        partials summed (fused steps: loss_rows of them) and the gradients all-reduced, then both optimizers"""
         head = self._adam_head(apply_update)
         self.side.join()
-        L.call("p2p_loss_partials_sum", _p(self.loss_part), 4, _p(self.losses), _stream())
-        self._reduce_tail()
+        if loss_rows:
+            L.call("p2p_loss_partials_sum", _p(self.loss_part), loss_rows, _p(self.losses), _stream())
+            self._reduce_tail()
         if apply_update:
             self.apply_adam(g_from=head)
+
+    def _finish_args(self, lambda_l1, lambda_hist=None, lambda_aux=None):
+        """p2p_finish_losses' (slot of the fourth generator term or -1, slot of the L1 term, weight of L1, weight of the fourth)"""
+        if self.head == "softmax":
+            # g_total = adv + 0 * l1 + lambda_seg * seg  (lambda_l1 is hard-wired to 0, pix2pix_model.py:263,273-278)
+            return 5, 6, 0.0, float(lambda_aux or 0.0)
+        return 4 if lambda_hist is not None else -1, 3, float(lambda_l1), float(lambda_hist) if lambda_hist is not None else 0.0
+
+    def _finish_step(self, loss_rows, finish_args, apply_update):
+        self._optimizer_tail(apply_update, loss_rows)
+        return self._write_losses(finish_args)
+
+    def _write_losses(self, finish_args):
+        """the result vector of a fused step from the loss slots"""
         out = self._new_out()
-        L.call("p2p_finish_losses", _p(self.losses), 4 if lambda_hist is not None else -1, 3, float(lambda_l1),
-               float(lambda_hist) if lambda_hist is not None else 0.0, self._slot_out, _stream())
+        L.call("p2p_finish_losses", _p(self.losses), *finish_args, self._slot_out, _stream())
         self.step_count += 1
         return out[:7]
 
@@ -1646,14 +1449,7 @@ class Pix2PixEngine:
         self._reduce_tail()
         if apply_update:
             self.apply_adam()
-        out = torch.empty(8, dtype=torch.float32, device=self.device)
-        if self.head == "softmax":
-            L.call("p2p_finish_losses", _p(self.losses), 5, 6, 0.0, float(lambda_aux or 0.0), _p(out), _stream())
-        else:
-            L.call("p2p_finish_losses", _p(self.losses), 4 if lambda_hist is not None else -1, 3, float(lambda_l1),
-                   float(lambda_hist) if lambda_hist is not None else 0.0, _p(out), _stream())
-        self.step_count += 1
-        return out[:7]
+        return self._write_losses(self._finish_args(lambda_l1, lambda_hist, lambda_aux))
 
     def _adam_head(self, apply_update):
         """Single-GPU steps: the main stream finishes the backward pass ~70 us before the weight-gradient stream does (the
@@ -1722,7 +1518,7 @@ class Pix2PixEngine:
 
     def _histogram_loss(self, P, B, Bg, lambda_hist, hist_allreduce):
         """Pix2PixHistogramModel.generator_loss (pix2pix_model.py:242-250): Hellinger(rgbuv_hist(real), rgbuv_hist(fake)).
-        Returns the gradient source lambda_hist * d(hist_loss)/d(fake) (three f32 slabs, one per colour component).
+        Returns the gradient source lambda_hist * d(hist_loss)/d(fake) (one f32 slab).
         The loss is sqrt(sum over the GLOBAL batch)/B_global, so under data parallelism the local sum of squares is
         all-reduced between the forward and the backward kernels."""
         S = self.S
@@ -1741,11 +1537,10 @@ class Pix2PixEngine:
         # of the loss scalars (like the element-mean losses) yields the global value
         L.call("p2p_hellinger_finish", _p(P["h_sq"]), (1.0 / Bg) * (B / Bg), _p(self.losses, 4), _stream())
         coef = float(lambda_hist) / (2.0 * math.sqrt(2.0) * Bg)
-        bwd3 = self.hist_fwd3 and self.hist_bwd3
-        L.call("p2p_rgbuv_hist_hellinger_bwd3" if bwd3 else "p2p_rgbuv_hist_hellinger_bwd", L.F32, B, S, S, C.byref(fake_view),
+        L.call("p2p_rgbuv_hist_hellinger_bwd3", L.F32, B, S, S, C.byref(fake_view),
                _p(P["h_real"]), _p(P["h_fake"]), _p(P["h_tot"][0]), _p(P["h_tot"][1]), _p(P["h_sq"]), coef, _p(P["h_gh"]),
                _p(P["h_dimg"]), _stream())
-        return L.GSrc(P["h_dimg"].data_ptr(), 2, 1 if bwd3 else 3, B * S * S * 4, 4, 0)
+        return L.GSrc(P["h_dimg"].data_ptr(), 2, 1, B * S * S * 4, 4, 0)
 
     def _hist_buffers(self, P, B):
         if "h_real" in P:
@@ -1778,14 +1573,13 @@ class Pix2PixEngine:
     HIST_POINT_CAP = 1024        # colour points kept per image; an image with more is contracted over its pixels
 
     def _hist_fwd(self, P, B, view, out, points):
-        """raw RGB-uv histograms [B][3][64][64] of a dense f32 image view (histogram.py:35-81 up to the normalisation).
-        points=True: the image is a palette sprite (the REAL image of a step) -- contract over its distinct colours."""
+        """raw RGB-uv histograms [B][3][64][64] of a dense f32 image view (histogram.py:35-81 up to the normalisation): three shared
+        kernel rows per pixel with all components in one workgroup, as in the backward kernel.  points=True: the image is a palette
+        sprite (the REAL image of a step) -- contract over its distinct colours.  (The per-component kernels remain in the library
+        as cross-checks: tests/test_hist_indexed_gpu.py calls them directly.)"""
         S = self.S
-        if not self.hist_fwd3:
-            L.call("p2p_rgbuv_hist_fwd", L.F32, B, S, S, C.byref(view), _p(out), _stream())
-            return
         pts = npts = NULL
-        if points and self.hist_points:
+        if points:
             L.call("p2p_rgbuv_points", L.F32, B, S, S, C.byref(view), self.HIST_POINT_CAP, _p(P["h_points"]), _p(P["h_npoints"]), _stream())
             pts, npts = _p(P["h_points"]), _p(P["h_npoints"])
         L.call("p2p_rgbuv_hist_fwd3", L.F32, B, S, S, C.byref(view), pts, npts, self.HIST_POINT_CAP, _p(out), _p(P["h_ws"]), _stream())
@@ -1807,31 +1601,13 @@ class Pix2PixEngine:
         assert self.head == "softmax" and self.in_ch == 1
         B = int(source_idx.shape[0])
         P = self.plan(B)
-        S = self.S
         Bg = global_batch or B
-        self._dp = dp
-        self._batch_offset = int(batch_offset)
+        self._dp, self._batch_offset = dp, int(batch_offset)
         src_t = self._to_device(source_idx, 1, B, is_int=True)
         real_t = self._to_device(real_idx, 1, B, is_int=True)
-        self._elide = self._elision()
-        try:
-            key = self._replay_key("indexed", B, masks, dp, apply_update, float(lambda_segmentation), Bg, int(batch_offset))
-            if key in self._replays:
-                return self._replay(key, P, src_t, real_t)
-            recording = self._begin_record(key)
-            if recording and dp is not None:
-                self._dp = _RecDP(dp)
-            try:
-                out = self._train_step_indexed_body(P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update)
-            except BaseException:
-                if recording:
-                    self._end_record(key, False)
-                raise
-            if recording:
-                self._end_record(key, True)
-            return out
-        finally:
-            self._elide = 0
+        return self._run_step("indexed", (float(lambda_segmentation), Bg, int(batch_offset)), P, src_t, real_t,
+                              lambda: self._train_step_indexed_body(P, B, Bg, src_t, real_t, lambda_segmentation, masks, apply_update),
+                              masks, apply_update)
 
     def _pack_indexed(self, P, B, src_t, real_t):
         S = self.S
@@ -1868,23 +1644,11 @@ class Pix2PixEngine:
                    C.byref(fake_view), float(lambda_segmentation) * inv_pix, inv_pix, C.byref(P["dz"].view()), NULL,
                    _p(self._softmax_part()), _p(self.losses, 5), _stream())
         self.discriminator_forward(P, 2 * B)
-        h2 = S // 2
-        L.call("p2p_bce_logits_pad8" if self.full_pixels else "p2p_bce_logits", self.dtype, 2 * B, B, h2, h2,
-               C.byref(P["logits"].view()), 1.0 / (Bg * h2 * h2), C.byref(P["dld"].view()), None, _p(self.loss_part), _stream())
+        self._bce_logits(P, B, Bg, None)
         P["skip_g_through_d"] = True
         self.discriminator_backward(P, B)
         self.generator_backward(P)
-        head = self._adam_head(apply_update)
-        self.side.join()
-        L.call("p2p_loss_partials_sum", _p(self.loss_part), 3, _p(self.losses), _stream())
-        self._reduce_tail()
-        if apply_update:
-            self.apply_adam(g_from=head)
-        out = self._new_out()
-        # g_total = adv + 0 * l1 + lambda_seg * seg  (lambda_l1 is hard-wired to 0, pix2pix_model.py:263,273-278)
-        L.call("p2p_finish_losses", _p(self.losses), 5, 6, 0.0, float(lambda_segmentation), self._slot_out, _stream())
-        self.step_count += 1
-        return out[:7]
+        return self._finish_step(3, self._finish_args(0.0, lambda_aux=lambda_segmentation), apply_update)
 
     def train_step_indexed_hooked(self, source_idx, real_idx, generator_loss, discriminator_loss, masks=None, apply_update=True):
         """Pix2PixIndexedModel.train_step (pix2pix_model.py:295-325) for a subclass that overrides the loss hooks (the palette-index
@@ -1899,7 +1663,7 @@ class Pix2PixEngine:
         assert self.head == "softmax" and self.in_ch == 1, "the RGBA models have train_step_rgba_hooked"
         B = int(source_idx.shape[0])
         P = self.plan(B)
-        S, h2, Cn = self.S, self.S // 2, self.out_ch
+        S, Cn = self.S, self.out_ch
         self._dp, self._batch_offset = None, 0
         src_t = self._to_device(source_idx, 1, B, is_int=True)
         real_t = self._to_device(real_idx, 1, B, is_int=True)
@@ -1918,19 +1682,14 @@ class Pix2PixEngine:
         onehot.zero_()
         onehot.view(-1, Cn).scatter_(1, real_t.view(-1, 1).long(), 1.0)
         self.discriminator_forward(P, 2 * B)
-        logits = P["logits"].t.detach().float().view(2 * B, h2, h2, 1)
-        lg_d = logits.clone().requires_grad_(True)
-        d_loss = discriminator_loss(lg_d[:B], lg_d[B:])
-        d_loss[0].backward()
-        lg_g = logits[B:].clone().requires_grad_(True)
+        d_loss, lg_d, lg_g = self._hook_discriminator(P, B, discriminator_loss)
         probs = probs32.detach().requires_grad_(True)
         probs._keras_logits = z32.detach().requires_grad_(True)
         g_loss = generator_loss(lg_g, probs, onehot)
         g_loss[0].backward()
         grad = lambda t: None if t.grad is None else t.grad.contiguous()        # noqa: E731  (absent: zero)
         gp, gz = grad(probs), grad(probs._keras_logits)
-        inner = slice(HALO, HALO + h2)
-        P["dld"].t[:, inner, inner, 0] = (torch.zeros_like(lg_d) if lg_d.grad is None else lg_d.grad).view(2 * B, h2, h2).to(self.tdt)
+        self._write_dlogits(P["dld"], lg_d)
         P["hook_keep"] = (gp, gz, lg_d, lg_g, probs)
         L.call("p2p_softmax_bwd", self.dtype, B, S, S, Cn, _p(probs32), NULL if gp is None else _p(gp), NULL if gz is None else _p(gz),
                1.0, C.byref(P["dz"].view()), _stream())
@@ -1938,14 +1697,8 @@ class Pix2PixEngine:
         P["head_dbias_done"] = False        # the plan is shared with the fused step, whose head sums the bias gradient itself
         self.discriminator_backward(P, B)
         self.generator_backward(P)
-        head = self._adam_head(apply_update)
-        self.side.join()
-        if apply_update:
-            self.apply_adam(g_from=head)
-        self.step_count += 1
-        vals = [g_loss[0], g_loss[1], g_loss[2], g_loss[3] if len(g_loss) > 3 else torch.zeros((), device=self.device),
-                d_loss[0], d_loss[1], d_loss[2]]
-        return torch.stack([v.detach().reshape(()).float() for v in vals])
+        self._optimizer_tail(apply_update)
+        return self._hooked_result(g_loss, d_loss)
 
     def _softmax_part(self):
         """workspace of p2p_softmax_cce_argmax: one (CCE, L1) partial per workgroup (include/p2pgan.h)"""
@@ -1956,14 +1709,16 @@ class Pix2PixEngine:
     def discriminate(self, target, source):
         """discriminator([target, source], training=True) (pix2pix_model.py:69-70): f32 device logits (B,S/2,S/2,1)."""
         B = int(target.shape[0])
-        P = self.plan(B)
-        S, ic, h2 = self.S, self.in_ch, self.S // 2
-        is_int = self.head == "softmax"
-        self._pack(P, self._to_device(target, ic, B, is_int), P["dcat"].view(coff=0), ic)
-        self._pack(P, self._to_device(source, ic, B, is_int), P["dcat"].view(coff=ic), ic)
-        self.discriminator_forward(P, B)
-        out = torch.empty((B, h2, h2, 1), dtype=torch.float32, device=self.device)
-        L.call("p2p_unpack", self.dtype, B, h2, h2, 1, C.byref(P["logits"].view()), _p(out), _stream())
+        return self._discriminate_pair(self.plan(B), B, target, source, self.head == "softmax")
+
+    def _discriminate_pair(self, P, N, first, second, is_int):
+        """[first, second] packed into P's discriminator input, D forward, the logits unpacked: f32 (N,S/2,S/2,1)"""
+        ic, h2 = self.in_ch, self.S // 2
+        self._pack(P, self._to_device(first, ic, N, is_int), P["dcat"].view(coff=0), ic)
+        self._pack(P, self._to_device(second, ic, N, is_int), P["dcat"].view(coff=ic), ic)
+        self.discriminator_forward(P, N)
+        out = torch.empty((N, h2, h2, 1), dtype=torch.float32, device=self.device)
+        L.call("p2p_unpack", self.dtype, N, h2, h2, 1, C.byref(P["logits"].view()), _p(out), _stream())
         return out
 
     def generate_indexed(self, source_idx, masks=None, with_probs=False):
@@ -2144,12 +1899,7 @@ class Pix2PixEngine:
         g = self._gradient_f32(d_image, (B, S, S, self.out_ch))
         gx = L.GSrc(g.data_ptr(), 2, 1, B * S * S * self.out_ch, self.out_ch, 0)
         fake = P["fake"].view()
-        if self.full_pixels and self.out_ch == 4 and self.dz_ch == 8:
-            L.call("p2p_tanh_l1_bwd_pad8", self.dtype, B, S, S, C.byref(fake), C.byref(fake), None, C.byref(gx), 0.0,
-                   C.byref(P["dz"].view()), _stream())
-        else:
-            L.call("p2p_tanh_l1_bwd", self.dtype, B, S, S, self.out_ch, C.byref(fake), C.byref(fake), None, C.byref(gx), 0.0,
-                   C.byref(P["dz"].view()), _stream())
+        self._tanh_l1_bwd(P, fake, fake, None, gx, 0.0)
         P["head_dbias_done"] = False
         self.generator_backward(P)
         d_src = None
@@ -2175,13 +1925,7 @@ class Pix2PixEngine:
 
     def tape_discriminator_forward(self, P, first, second):
         """discriminator([first, second], training=True) on arena P: f32 logits (N,S/2,S/2,1)"""
-        N, S, ic, h2 = P["B"], self.S, self.in_ch, self.S // 2
-        self._pack(P, self._to_device(first, ic, N), P["dcat"].view(coff=0), ic)
-        self._pack(P, self._to_device(second, ic, N), P["dcat"].view(coff=ic), ic)
-        self.discriminator_forward(P, N)
-        out = torch.empty((N, h2, h2, 1), dtype=torch.float32, device=self.device)
-        L.call("p2p_unpack", self.dtype, N, h2, h2, 1, C.byref(P["logits"].view()), _p(out), _stream())
-        return out
+        return self._discriminate_pair(P, P["B"], first, second, False)
 
     def tape_discriminator_backward(self, P, d_logits, weights, need_first, need_second):
         """VJP of one standalone discriminator call (discriminator_backward for one input pair): with `weights`, the weight

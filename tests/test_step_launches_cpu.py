@@ -173,3 +173,35 @@ def test_variant_key_drops_the_batch_and_keeps_the_plan():
     assert k[16] != k[17], "the split-K target step at B <= 16 changes no variant key"
     names = {key[0] for key in k[40]}
     assert {"p2p_igemm", "p2p_wgemm", "p2p_wgrad_small", "p2p_norm_act_fwd", "p2p_norm_act_bwd", "p2p_conv_fewin"} <= names
+
+
+# ---------------------------------------------------------------------------------------------------------------- switch table
+def test_every_switch_of_the_table_is_in_the_replay_key():
+    """A recorded step holds its kernel choices by value, so every entry of engine.SWITCHES must change the switch part of the
+    replay key when it is flipped to another legal value; the same settings give the same key."""
+    import inspect
+    from palette_and_histo_gan_amd import engine as E
+    eng = SL.Census("baseline", 64, "bf16").eng
+    assert "_SWITCH_VALUES(self)" in inspect.getsource(E.Pix2PixEngine._replay_key)
+    base = E._SWITCH_VALUES(eng)
+    assert len(base) == len(E.SWITCHES) and E._SWITCH_VALUES(eng) == base
+    for attr, _, default, _ in E.SWITCHES:
+        obj, name = E._switch_holder(eng, attr)
+        old = getattr(obj, name)
+        assert type(old) is type(default), attr
+        setattr(obj, name, (not old) if isinstance(old, bool) else (1 - old if old in (0, 1) else 2 * old))
+        try:
+            assert E._SWITCH_VALUES(eng) != base, f"flipping {attr} leaves the replay key as it was"
+        finally:
+            setattr(obj, name, old)
+    assert E._SWITCH_VALUES(eng) == base
+
+
+def test_engine_reads_the_environment_only_through_the_switch_table():
+    """one read of the environment in engine.py: the loop over the table in Pix2PixEngine.__init__"""
+    import inspect
+    from palette_and_histo_gan_amd import engine as E
+    assert inspect.getsource(E).count("os.environ") == 1 and "getenv" not in inspect.getsource(E)
+    init = inspect.getsource(E.Pix2PixEngine.__init__)
+    loop = init.index("for attr, env, default, parse in SWITCHES + GATES:")
+    assert loop < init.index("os.environ") < init.index("setattr(obj, name", loop)
