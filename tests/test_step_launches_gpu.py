@@ -95,7 +95,7 @@ from tests import step_launches as SL
 
 pytestmark = pytest.mark.gpu
 
-OUT_TOL = {L.F32: 2e-5, L.BF16: 6e-3}      # test_kernels_gpu.py: activation-dtype outputs
+OUT_TOL = SL.OUT_TOL                        # test_kernels_gpu.py: activation-dtype outputs
 F32_TOL = 2e-5                              # f32 slabs / statistics of short contractions (test_kernels_gpu.py)
 SENTINEL = -1234.5                          # exact in bf16 and f32
 TAIL = 256                                  # elements of sentinel behind every output buffer
