@@ -186,6 +186,118 @@ int p2p_wgrad_small(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd
 long long p2p_view_colsum_workspace_bytes(int dtype, int N, int H, int W, int C, const p2p_tensor* v);
 int p2p_view_colsum(int dtype, int N, int H, int W, int C, const p2p_tensor* v, float* out, float* workspace, void* stream);
 
+/* ---- route queries: which kernel a launcher would start -------------------------------------- */
+
+/* The launchers above and p2p_norm_act_fwd / _bwd below choose among template instantiations and kernel forms from their
+ * arguments and from A/B switches read once per process from the environment (README, "Tuning / A-B switches").  Each query
+ * here takes the launch's arguments (views need their geometry only; pointers their null-ness and 16-byte alignment), calls
+ * the SAME decision function as its launcher, starts nothing and needs no GPU.  It returns a small code composed by the macro
+ * next to it, or -1 where the launcher would refuse the arguments.  The P2P_*_ARMS lists name every arm the launchers'
+ * dispatch has, as X(fields of the macro): tests/test_switch_routes_cpu.py requires each to be run by a GPU test or named
+ * unreachable with a reason. */
+
+/* p2p_igemm (p2p_igemm_route; P2P_IGEMM_ROUTE_BRIG: the block-resident kernel takes the layer, see p2p_brig_route) and
+ * p2p_igemm_edge: kernel family, BM x BN tile, K groups per tile, LDS stages, block order (w_major: blocks that share a
+ * weight tile are neighbours). */
+#define P2P_IGEMM_FAM_R03 1      /* igemm_kernel<GEN = false>: power-of-two K bytes, no bias / activation / column mask */
+#define P2P_IGEMM_FAM_GEN 2      /* igemm_kernel<GEN = true> */
+#define P2P_IGEMM_FAM_PIPE_G 3   /* igemm_pipe_kernel<MODE 0>: software-pipelined, op G */
+#define P2P_IGEMM_FAM_PIPE_P 4   /* igemm_pipe_kernel<MODE 1>: op P */
+#define P2P_IGEMM_TILE_128x128 0
+#define P2P_IGEMM_TILE_256x128 1
+#define P2P_IGEMM_TILE_128x64 2
+#define P2P_IGEMM_TILE_256x64 3
+#define P2P_IGEMM_TILE_128x32 4
+#define P2P_IGEMM_TILE_256x32 5
+#define P2P_IGEMM_ROUTE(family, tile, kgroups, stages, w_major) \
+    ((family) | ((tile) << 3) | (((kgroups) - 1) << 6) | (((stages) - 2) << 7) | ((w_major) << 9))
+#define P2P_IGEMM_ROUTE_BRIG 0
+/* X(family, tile, K groups, stages); every arm exists with w_major 0 and 1 */
+#define P2P_IGEMM_ARMS(X) \
+    X(1, 0, 1, 2) X(1, 0, 1, 3) X(1, 1, 1, 2) X(1, 1, 1, 3) X(1, 2, 1, 2) X(1, 2, 1, 3) \
+    X(1, 3, 1, 2) X(1, 3, 1, 3) X(1, 4, 1, 2) X(1, 4, 1, 3) X(1, 5, 1, 2) X(1, 5, 1, 3) \
+    X(2, 0, 1, 2) X(2, 0, 1, 3) X(2, 1, 1, 2) X(2, 1, 1, 3) X(2, 2, 1, 2) X(2, 2, 1, 3) \
+    X(2, 3, 1, 2) X(2, 3, 1, 3) X(2, 4, 1, 2) X(2, 4, 1, 3) X(2, 5, 1, 2) X(2, 5, 1, 3) \
+    X(3, 1, 1, 3) X(3, 0, 2, 4) X(3, 0, 1, 2) X(4, 1, 1, 3) X(4, 0, 2, 4) X(4, 0, 1, 2)
+int p2p_igemm_route(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi, const p2p_tensor* lo,
+                    int splitk, int with_stats);
+int p2p_igemm_edge_route(int op, int stride, int dtype, int N, int LH, int LW, int cin_pad, int ncols, int w_rows,
+                         const p2p_tensor* in, const p2p_tensor* out, int with_bias, int act);
+
+/* brig_launch, through p2p_igemm (fused 0) or p2p_igemm_norm_act (fused 1): op, output channels per wave (cbw 1: 32, 2: 64),
+ * DMA issue order of waves 4-7 (stagger), fused InstanceNorm + activation epilogue.  P2P_BRIG_ROUTE_NONE: the kernel (fused 1:
+ * its fused epilogue) is not offered for the shape. */
+#define P2P_BRIG_ROUTE(op_p, cbw, stagger, fused) (1 | ((op_p) << 1) | (((cbw) - 1) << 2) | ((stagger) << 3) | ((fused) << 4))
+#define P2P_BRIG_ROUTE_NONE 0
+/* X(op P, cbw, stagger, fused) */
+#define P2P_BRIG_ARMS(X) \
+    X(0, 1, 0, 0) X(0, 1, 0, 1) X(0, 1, 1, 0) X(0, 1, 1, 1) X(0, 2, 0, 0) X(0, 2, 0, 1) X(0, 2, 1, 0) X(0, 2, 1, 1) \
+    X(1, 1, 0, 0) X(1, 1, 0, 1) X(1, 1, 1, 0) X(1, 1, 1, 1) X(1, 2, 0, 0) X(1, 2, 0, 1) X(1, 2, 1, 0) X(1, 2, 1, 1)
+int p2p_brig_route(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, int fused);
+
+/* p2p_wgemm / p2p_wgemm_edge: the software-pipelined bf16 kernel, or wgemm_kernel on a BG x BD tile */
+#define P2P_WGEMM_ROUTE_PIPE 0
+#define P2P_WGEMM_ROUTE_128x128 1
+#define P2P_WGEMM_ROUTE_64x128 2
+#define P2P_WGEMM_ROUTE_32x128 3
+#define P2P_WGEMM_ROUTE_64x64 4
+#define P2P_WGEMM_ROUTE_32x64 5
+#define P2P_WGEMM_ROUTE_64x32 6
+#define P2P_WGEMM_ROUTE_32x32 7
+#define P2P_WGEMM_ARMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+int p2p_wgemm_route(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi, const p2p_tensor* lo,
+                    int msplit);
+
+/* p2p_wgrad_small: stride, GT x DT window of 32x32 tiles, waves per workgroup (16: one tap each, 8: two taps each), packing of
+ * few-channel pixels (0 none, 1 the hi side, 2 the lo side), bank swizzle of the transposing LDS reads (1: a mask is in force on
+ * either side) */
+#define P2P_WS_TILE_1x1 0
+#define P2P_WS_TILE_1x2 1
+#define P2P_WS_TILE_1x4 2
+#define P2P_WS_TILE_2x1 3
+#define P2P_WS_TILE_2x2 4
+#define P2P_WS_ROUTE(stride, tile, waves, pack, swizzle) \
+    (((stride) - 1) | ((tile) << 1) | (((waves) >> 4) << 4) | ((pack) << 5) | ((swizzle) << 7))
+/* X(stride, tile, waves, pack, swizzle): unpacked windows in both wave counts with and without the swizzle; packed layers (8 waves,
+ * no swizzle): pack 1 on the 1x2 window, pack 2 on the 2x1 window at stride 1 */
+#define P2P_WS_ARMS(X) \
+    X(1, 0, 8, 0, 0) X(1, 0, 8, 0, 1) X(1, 0, 16, 0, 0) X(1, 0, 16, 0, 1) X(1, 1, 8, 0, 0) X(1, 1, 8, 0, 1) X(1, 1, 16, 0, 0) X(1, 1, 16, 0, 1) \
+    X(1, 2, 8, 0, 0) X(1, 2, 8, 0, 1) X(1, 2, 16, 0, 0) X(1, 2, 16, 0, 1) X(1, 3, 8, 0, 0) X(1, 3, 8, 0, 1) X(1, 3, 16, 0, 0) X(1, 3, 16, 0, 1) \
+    X(1, 4, 8, 0, 0) X(1, 4, 8, 0, 1) X(1, 4, 16, 0, 0) X(1, 4, 16, 0, 1) \
+    X(2, 0, 8, 0, 0) X(2, 0, 8, 0, 1) X(2, 0, 16, 0, 0) X(2, 0, 16, 0, 1) X(2, 1, 8, 0, 0) X(2, 1, 8, 0, 1) X(2, 1, 16, 0, 0) X(2, 1, 16, 0, 1) \
+    X(2, 2, 8, 0, 0) X(2, 2, 8, 0, 1) X(2, 2, 16, 0, 0) X(2, 2, 16, 0, 1) X(2, 3, 8, 0, 0) X(2, 3, 8, 0, 1) X(2, 3, 16, 0, 0) X(2, 3, 16, 0, 1) \
+    X(2, 4, 8, 0, 0) X(2, 4, 8, 0, 1) X(2, 4, 16, 0, 0) X(2, 4, 16, 0, 1) \
+    X(1, 1, 8, 1, 0) X(2, 1, 8, 1, 0) X(1, 3, 8, 2, 0)
+int p2p_wgrad_small_route(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, int hi_ld, int lo_ld);
+
+/* p2p_norm_act_fwd / _fwd_tail / _bwd: the form (lane groups on maps of <= 16 pixels; register-resident; the workgroup forms:
+ * one pass, statistics pass + apply pass over a pixel split, apply-only over statistics slots of a conv epilogue; the scalar
+ * kernel), pixels per thread of the small / register forms, the f32-slab loader instantiation (forward: raw_kind 2, backward:
+ * a gradient source of kind 2) and log2 of the channel group (a launch argument, not an instantiation: P2P_NORM_ROUTE_ARM
+ * strips it). */
+#define P2P_NORM_FORM_SCALAR 0
+#define P2P_NORM_FORM_SMALL 1
+#define P2P_NORM_FORM_REG 2
+#define P2P_NORM_FORM_VEC0 3
+#define P2P_NORM_FORM_VEC12 4
+#define P2P_NORM_FORM_VEC3 5
+#define P2P_NORM_ROUTE(form, ppl, slabs, lg_cg) ((form) | ((ppl) << 3) | ((slabs) << 7) | ((lg_cg) << 8))
+#define P2P_NORM_ROUTE_ARM(code) ((code) & 0xff)
+/* X(form, pixels per thread, slab loader) */
+#define P2P_NORM_FWD_ARMS(X) \
+    X(0, 0, 0) X(1, 1, 0) X(1, 1, 1) X(1, 2, 0) X(1, 2, 1) X(1, 4, 0) X(1, 4, 1) \
+    X(2, 1, 0) X(2, 1, 1) X(2, 2, 0) X(2, 2, 1) X(2, 4, 0) X(2, 4, 1) X(2, 8, 0) X(2, 8, 1) X(3, 0, 0) X(4, 0, 0) X(5, 0, 0)
+#define P2P_NORM_BWD_ARMS(X) \
+    X(0, 0, 0) X(1, 1, 0) X(1, 1, 1) X(1, 2, 0) X(1, 2, 1) X(1, 4, 0) X(1, 4, 1) \
+    X(2, 1, 0) X(2, 1, 1) X(2, 2, 0) X(2, 2, 1) X(2, 4, 0) X(2, 4, 1) X(2, 8, 0) X(2, 8, 1) X(3, 0, 0) X(4, 0, 0)
+int p2p_norm_act_fwd_route(int dtype, int N, int H, int W, int C, const void* raw, int raw_kind, int nslabs,
+                           long long slab_stride, const float* gamma, const float* beta, const p2p_tensor* out,
+                           void* raw_out, float* stats, float* ws, long long ws_bytes, int nsplit,
+                           const p2p_tensor* tail, int tail_ch);
+int p2p_norm_act_bwd_route(int dtype, int N, int H, int W, int C, const void* raw, const float* stats, const float* gamma,
+                           const float* beta, const p2p_gsrc* g1, const p2p_gsrc* g2, const p2p_tensor* draw,
+                           float* dgamma_part, float* dbeta_part, float* ws, long long ws_bytes, int nsplit);
+
 /* ---- InstanceNorm + activation + dropout (networks.py:18-19,29-34), fused ---------------------- */
 
 /* raw: conv output, dense [N*H*W][C]; raw_kind 1 = `dtype`, 2 = f32 with nslabs split-K slabs.

@@ -130,6 +130,14 @@ SPECIAL = {"p2p_last_error": ([], C.c_char_p),
            "p2p_conv_strip_stat_slots": ([_i, _i, _i, _i, _i, _i, _i], C.c_int),
            "p2p_conv_fewout_ok": ([_i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
            "p2p_wgrad_small_blocks": ([_i, _i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
+           # which kernel a launcher would start (include/p2pgan.h "route queries")
+           "p2p_igemm_route": ([_i, _i, _i, _i, _i, _i, _i, _TP, _TP, _i, _i], C.c_int),
+           "p2p_igemm_edge_route": ([_i, _i, _i, _i, _i, _i, _i, _i, _i, _TP, _TP, _i, _i], C.c_int),
+           "p2p_brig_route": ([_i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
+           "p2p_wgemm_route": ([_i, _i, _i, _i, _i, _i, _i, _TP, _TP, _i], C.c_int),
+           "p2p_wgrad_small_route": ([_i, _i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
+           "p2p_norm_act_fwd_route": ([_i, _i, _i, _i, _i, _vp, _i, _i, _ll, _vp, _vp, _TP, _vp, _vp, _vp, _ll, _i, _TP, _i], C.c_int),
+           "p2p_norm_act_bwd_route": ([_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _GP, _GP, _TP, _vp, _vp, _vp, _ll, _i], C.c_int),
            "p2p_wgemm_workspace_bytes": ([_i, _i, _i, _i, _i, _i], C.c_longlong),
            "p2p_rgbuv_hist_fwd3_workspace_bytes": ([_i], C.c_longlong),
            "p2p_soft_palette_workspace_bytes": ([_i, _i, _i], C.c_longlong),

@@ -583,6 +583,20 @@ extern "C" int p2p_brig_stat_slots(int op, int dtype, int N, int LH, int LW, int
     return p.ok ? p.slots : 0;
 }
 
+// DMA issue order of the weight ring (P2P_BRIG_STAGGER=0: every wave issues in the same order) and the fused-epilogue switch
+static int brig_stagger() {
+    static int sg = -1;
+    if (sg < 0) { const char* e = getenv("P2P_BRIG_STAGGER"); sg = e ? atoi(e) : 1; }
+    return sg;
+}
+static int brig_fuse_norm_on() {
+    static int en = -1;
+    if (en < 0) { const char* e = getenv("P2P_BRIG_FUSE_NORM"); en = e ? atoi(e) : 1; }
+    return en;
+}
+// kernel instantiation of a plan: bit 1 = op P, bit 0 = 64 output channels per wave
+static int brig_key(int op, const BrigPlan& p) { return (op == P2P_OP_P ? 2 : 0) + (p.cbw == 2 ? 1 : 0); }
+
 struct BrigNorm { const float* gamma; const float* beta; float eps; int act; float alpha; const p2p_tensor* act_out; float* stats; };
 
 int brig_launch(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi, const p2p_tensor* lo,
@@ -615,7 +629,7 @@ int brig_launch(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const 
         a.act_out = (char*)norm->act_out->ptr; a.act_img = norm->act_out->img_stride; a.act_row = norm->act_out->row_stride; a.act_ld = norm->act_out->ld;
         a.norm_stats = norm->stats;
     }
-    { static int sg = -1; if (sg < 0) { const char* e = getenv("P2P_BRIG_STAGGER"); sg = e ? atoi(e) : 1; } a.stagger = sg; }
+    a.stagger = brig_stagger();
     // per-lane gather offsets are 32-bit, counted from the lowest address a block touches (row -1, column -1 of image 0)
     a.in_lo = -((long long)in->row_stride + 1) * in->ld * 2;
     const long long span = ((long long)(N - 1) * in->img_stride + (long long)(op == P2P_OP_P ? LH + 1 : 2 * LH + 1) * in->row_stride +
@@ -623,7 +637,7 @@ int brig_launch(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const 
     P2P_REQUIRE(span < 0xffffffffLL && (long long)16 * a.ncols * a.C * 2 < 0xffffffffLL, "p2p_brig: view larger than 4 GB");
     const dim3 grid((unsigned)(p.ntiles * p.nnt));
     hipStream_t st = (hipStream_t)stream;
-    const int key = (op == P2P_OP_P ? 2 : 0) + (p.cbw == 2 ? 1 : 0);
+    const int key = brig_key(op, p);
 #define BRIG_GO(M, CB, R)                                                                                                          \
     do {                                                                                                                           \
         static bool attr = false;                                                                                                  \
@@ -644,9 +658,18 @@ int brig_launch(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const 
 // shapes whose workgroups hold whole images.  1 if p2p_igemm_norm_act takes the shape.
 extern "C" int p2p_igemm_norm_act_ok(int op, int dtype, int N, int LH, int LW, int Cg, int Cd) {
     const BrigPlan p = brig_plan(op, dtype, N, LH, LW, Cg, Cd);
-    static int en = -1;
-    if (en < 0) { const char* e = getenv("P2P_BRIG_FUSE_NORM"); en = e ? atoi(e) : 1; }
-    return p.ok && p.tiles_per_img == 1 && en;
+    return p.ok && p.tiles_per_img == 1 && brig_fuse_norm_on();
+}
+
+// Host query: the instantiation brig_launch would start for the layer (P2P_BRIG_ROUTE of include/p2pgan.h) -- through p2p_igemm
+// (fused == 0) or through p2p_igemm_norm_act (fused == 1) -- or P2P_BRIG_ROUTE_NONE where the block-resident kernel (fused == 1:
+// its fused epilogue) is not offered for the shape and the caller takes the im2col route (p2p_igemm_route).
+extern "C" int p2p_brig_route(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, int fused) {
+    const BrigPlan p = brig_plan(op, dtype, N, LH, LW, Cg, Cd);
+    if (!p.ok) return P2P_BRIG_ROUTE_NONE;
+    if (fused && !p2p_igemm_norm_act_ok(op, dtype, N, LH, LW, Cg, Cd)) return P2P_BRIG_ROUTE_NONE;
+    const int key = brig_key(op, p);
+    return P2P_BRIG_ROUTE(key >> 1, (key & 1) + 1, brig_stagger() ? 1 : 0, fused ? 1 : 0);
 }
 
 extern "C" int p2p_igemm_norm_act(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi,

@@ -717,17 +717,19 @@ static int igemm_bm(long long M, int ctiles, unsigned gz) {
     return M >= 256 * 512 ? 256 : 128;
 }
 
+// The instantiation a launch starts (P2P_IGEMM_* of include/p2pgan.h): decided by igemm_route from the launch arguments and the
+// cached switches, started by igemm_launch, reported by p2p_igemm_route / p2p_igemm_edge_route.
+struct IgemmRoute { int family, tile, kg, nst; };
+
+static int igemm_route_code(const IgemmRoute& r, int w_major) {
+    return P2P_IGEMM_ROUTE(r.family, r.tile, r.kg, r.nst, w_major);
+}
+
 template <typename T, int WM, int WN, int TM, int TN, bool GEN>
-static void igemm_go(IgemmArgs& a, unsigned gz, bool vepi, hipStream_t st) {
+static void igemm_go(IgemmArgs& a, unsigned gz, bool vepi, int nst, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NTHR = WM * WN * 64;
     const int ctiles = (a.ncols + 31) / 32 * 32;
     dim3 grid((a.M + BM - 1) / BM, (ctiles + BN - 1) / BN, gz);
-    // three LDS stages when the launch cannot put two workgroups on every CU anyway (<= 320 workgroups) and the
-    // K loop is long enough to fill the ring
-    const long long nblk = (long long)grid.x * grid.y * grid.z;
-    const int nkb_host = (a.taps_per * a.C * (int)sizeof(T)) >> 7;
-    int nst = ((nblk <= 320 || NTHR == 512) && nkb_host >= 4) ? 3 : 2;   // 8-wave tiles: one workgroup per CU by design
-    if (3 * (size_t)(BM + BN) * 128 > 150 * 1024) nst = 2;
     size_t stage = (size_t)nst * (BM + BN) * 128;
     size_t epi = (size_t)BM * (BN * 4 + 16) + 4096;    // f32 staging of the epilogue is the larger case (+ stats scratch)
     size_t shm = vepi ? (stage > epi ? stage : epi) : stage;
@@ -744,6 +746,17 @@ static void igemm_go(IgemmArgs& a, unsigned gz, bool vepi, hipStream_t st) {
         if (vepi) igemm_kernel<T, WM, WN, TM, TN, GEN, true, 2><<<grid, dim3(NTHR), shm, st>>>(a);
         else igemm_kernel<T, WM, WN, TM, TN, GEN, false, 2><<<grid, dim3(NTHR), shm, st>>>(a);
     }
+}
+
+// LDS stages of igemm_kernel on a bm x bn tile of nthr threads: three when the launch cannot put two workgroups on every CU
+// anyway (<= 320 workgroups) and the K loop is long enough to fill the ring
+static int igemm_stages(const IgemmArgs& a, int esz, unsigned gz, int bm, int bn, int nthr) {
+    const int ctiles = (a.ncols + 31) / 32 * 32;
+    const long long nblk = (long long)((a.M + bm - 1) / bm) * ((ctiles + bn - 1) / bn) * gz;
+    const int nkb_host = (a.taps_per * a.C * esz) >> 7;
+    int nst = ((nblk <= 320 || nthr == 512) && nkb_host >= 4) ? 3 : 2;   // 8-wave tiles: one workgroup per CU by design
+    if (3 * (size_t)(bm + bn) * 128 > 150 * 1024) nst = 2;
+    return nst;
 }
 
 // Software-pipelined form: 0 = off (the r03 kernel for every shape), 1 = automatic choice, 2 = always two K groups per 128x128
@@ -766,50 +779,70 @@ static void igemm_pipe_go(IgemmArgs& a, unsigned gz, bool vepi, hipStream_t st) 
     else igemm_pipe_kernel<T, MODE, WM, WN, TM, TN, KG, NST, false><<<grid, dim3(NTHR), shm, st>>>(a);
 }
 
-// The pipelined kernel takes the launch when K-blocks lie inside one tap, the columns fill 128-wide tiles and the op is a
-// stride-2 G or P; returns false otherwise (the caller falls back to igemm_kernel).
+// The one decision of the launcher.  The pipelined kernel takes the launch when K-blocks lie inside one tap, the columns fill
+// 128-wide tiles and the op is a stride-2 G or P; igemm_kernel takes everything else.
+static IgemmRoute igemm_route(const IgemmArgs& a, int esz, bool gen, unsigned gz) {
+    const int ctiles = (a.ncols + 31) / 32 * 32;      // launched columns (<= w_rows)
+    const bool bigM = a.M >= 256 * 512;                // enough rows to fill the chip with 256-row tiles
+    IgemmRoute r = {gen ? P2P_IGEMM_FAM_GEN : P2P_IGEMM_FAM_R03, P2P_IGEMM_TILE_128x128, 1, 2};
+    if (!gen) {
+        // (32-bit per-lane gather offsets: the gathered view and the weights must each span less than 4 GB)
+        const long long in_span = ((long long)((a.M >> (a.lgLW + a.lgLH)) + 1) * a.in_img + 4LL * a.in_row + 4) * a.in_ld * (long long)esz;
+        const long long w_span = 16LL * a.w_rows * a.C * (long long)esz;
+        if (igemm_pipe_mode() && a.lgCB >= 7 && ctiles % 128 == 0 && a.mode <= 1 && in_span < 0xffffffffLL && w_span < 0xffffffffLL) {
+            r.family = a.mode == 0 ? P2P_IGEMM_FAM_PIPE_G : P2P_IGEMM_FAM_PIPE_P;
+            const int bm = igemm_bm(a.M, ctiles, gz);
+            const int pm = igemm_pipe_mode();
+            // f32 (parity mode) without fused statistics: ONE variant whatever the pixel count, so that a pixel's sum does not depend on
+            // the batch it sits in (engine.batch_invariant)
+            const bool fixed = esz == 4 && a.stat_part == nullptr && pm == 1;
+            if (bm == 256 && !fixed) { r.tile = P2P_IGEMM_TILE_256x128; r.kg = 1; r.nst = 3; return r; }
+            const long long tiles = ((a.M + 127) / 128) * (long long)(ctiles / 128) * gz;
+            const bool kg2 = fixed || pm == 2 || (pm != 3 && tiles <= 384);      // one workgroup per CU anyway: the second wave of a SIMD splits K
+            r.kg = kg2 ? 2 : 1; r.nst = kg2 ? 4 : 2;
+            return r;
+        }
+    }
+    int bm, bn, nthr;
+    if (igemm_bm(a.M, ctiles, gz) == 256 && ctiles % 128 == 0) { r.tile = P2P_IGEMM_TILE_256x128; bm = 256; bn = 128; nthr = 512; }
+    // 128x128: eight waves (32x64 each), i.e. twice the waves per SIMD for the same LDS: +12 % over four 64x64 waves
+    // (r01, A/B on one device); the 64- and 32-column tiles measured no better with eight waves and keep four
+    else if (ctiles % 128 == 0) { r.tile = P2P_IGEMM_TILE_128x128; bm = 128; bn = 128; nthr = 512; }
+    else if (ctiles % 64 == 0) {
+        if (bigM) { r.tile = P2P_IGEMM_TILE_256x64; bm = 256; bn = 64; }
+        else { r.tile = P2P_IGEMM_TILE_128x64; bm = 128; bn = 64; }
+        nthr = 256;
+    } else {
+        if (bigM) { r.tile = P2P_IGEMM_TILE_256x32; bm = 256; bn = 32; }
+        else { r.tile = P2P_IGEMM_TILE_128x32; bm = 128; bn = 32; }
+        nthr = 256;
+    }
+    r.nst = igemm_stages(a, esz, gz, bm, bn, nthr);
+    return r;
+}
+
 template <typename T, int MODE>
-static bool igemm_pipe_try(IgemmArgs& a, unsigned gz, bool vepi, hipStream_t st) {
-    const int ctiles = (a.ncols + 31) / 32 * 32;
-    const int nkb = (a.taps_per * a.C * (int)sizeof(T)) >> 7;
-    const int bm = igemm_bm(a.M, ctiles, gz);
-    const int pm = igemm_pipe_mode();
-    // f32 (parity mode) without fused statistics: ONE variant whatever the pixel count, so that a pixel's sum does not depend on
-    // the batch it sits in (engine.batch_invariant)
-    const bool fixed = sizeof(T) == 4 && a.stat_part == nullptr && pm == 1;
-    if (bm == 256 && !fixed) { igemm_pipe_go<T, MODE, 4, 2, 2, 2, 1, 3>(a, gz, vepi, st); return true; }
-    const long long tiles = ((a.M + 127) / 128) * (long long)(ctiles / 128) * gz;
-    (void)nkb;
-    const bool kg2 = fixed || pm == 2 || (pm != 3 && tiles <= 384);      // one workgroup per CU anyway: the second wave of a SIMD splits K
-    if (kg2) igemm_pipe_go<T, MODE, 2, 2, 2, 2, 2, 4>(a, gz, vepi, st);
+static void igemm_pipe_start(IgemmArgs& a, const IgemmRoute& r, unsigned gz, bool vepi, hipStream_t st) {
+    if (r.tile == P2P_IGEMM_TILE_256x128) igemm_pipe_go<T, MODE, 4, 2, 2, 2, 1, 3>(a, gz, vepi, st);
+    else if (r.kg == 2) igemm_pipe_go<T, MODE, 2, 2, 2, 2, 2, 4>(a, gz, vepi, st);
     else igemm_pipe_go<T, MODE, 2, 2, 2, 2, 1, 2>(a, gz, vepi, st);
-    return true;
 }
 
 template <typename T, bool GEN>
 static int igemm_launch(IgemmArgs& a, int phases, bool vepi, hipStream_t st) {
     unsigned gz = (unsigned)(phases * a.splitk);
-    const int ctiles = (a.ncols + 31) / 32 * 32;      // launched columns (<= w_rows)
-    const bool bigM = a.M >= 256 * 512;                // enough rows to fill the chip with 256-row tiles
+    const IgemmRoute r = igemm_route(a, (int)sizeof(T), GEN, gz);
     if constexpr (!GEN) {
-        // (32-bit per-lane gather offsets: the gathered view and the weights must each span less than 4 GB)
-        const long long in_span = ((long long)((a.M >> (a.lgLW + a.lgLH)) + 1) * a.in_img + 4LL * a.in_row + 4) * a.in_ld * (long long)sizeof(T);
-        const long long w_span = 16LL * a.w_rows * a.C * (long long)sizeof(T);
-        if (igemm_pipe_mode() && a.lgCB >= 7 && ctiles % 128 == 0 && a.mode <= 1 && in_span < 0xffffffffLL && w_span < 0xffffffffLL) {
-            const bool ok = a.mode == 0 ? igemm_pipe_try<T, 0>(a, gz, vepi, st) : igemm_pipe_try<T, 1>(a, gz, vepi, st);
-            if (ok) return p2p_check_launch("p2p_igemm");
-        }
+        if (r.family == P2P_IGEMM_FAM_PIPE_G) { igemm_pipe_start<T, 0>(a, r, gz, vepi, st); return p2p_check_launch("p2p_igemm"); }
+        if (r.family == P2P_IGEMM_FAM_PIPE_P) { igemm_pipe_start<T, 1>(a, r, gz, vepi, st); return p2p_check_launch("p2p_igemm"); }
     }
-    if (igemm_bm(a.M, ctiles, gz) == 256 && ctiles % 128 == 0) igemm_go<T, 4, 2, 2, 2, GEN>(a, gz, vepi, st);
-    // 128x128: eight waves (32x64 each), i.e. twice the waves per SIMD for the same LDS: +12 % over four 64x64 waves
-    // (r01, A/B on one device); the 64- and 32-column tiles measured no better with eight waves and keep four
-    else if (ctiles % 128 == 0) igemm_go<T, 4, 2, 1, 2, GEN>(a, gz, vepi, st);
-    else if (ctiles % 64 == 0) {
-        if (bigM) igemm_go<T, 4, 1, 2, 2, GEN>(a, gz, vepi, st);
-        else igemm_go<T, 2, 2, 2, 1, GEN>(a, gz, vepi, st);
-    } else {
-        if (bigM) igemm_go<T, 4, 1, 2, 1, GEN>(a, gz, vepi, st);
-        else igemm_go<T, 4, 1, 1, 1, GEN>(a, gz, vepi, st);
+    switch (r.tile) {
+        case P2P_IGEMM_TILE_256x128: igemm_go<T, 4, 2, 2, 2, GEN>(a, gz, vepi, r.nst, st); break;
+        case P2P_IGEMM_TILE_128x128: igemm_go<T, 4, 2, 1, 2, GEN>(a, gz, vepi, r.nst, st); break;
+        case P2P_IGEMM_TILE_256x64: igemm_go<T, 4, 1, 2, 2, GEN>(a, gz, vepi, r.nst, st); break;
+        case P2P_IGEMM_TILE_128x64: igemm_go<T, 2, 2, 2, 1, GEN>(a, gz, vepi, r.nst, st); break;
+        case P2P_IGEMM_TILE_256x32: igemm_go<T, 4, 1, 2, 1, GEN>(a, gz, vepi, r.nst, st); break;
+        default: igemm_go<T, 4, 1, 1, 1, GEN>(a, gz, vepi, r.nst, st); break;
     }
     return p2p_check_launch("p2p_igemm");
 }
@@ -820,7 +853,7 @@ extern "C" int p2p_igemm_stat_slots(int op, int N, int LH, int LW, int ncols);
 // view (whole 16-byte chunks), w_rows = rows per weight tap slab (multiple of 32, >= the launched columns).
 static int igemm_common(int op, int stride, int dtype, int N, int LH, int LW, int C, int ncols, int w_rows,
                         const p2p_tensor* in, const p2p_tensor* out, const void* w, const float* bias, int act,
-                        float alpha, int splitk, float* slabs, float* stat_part, void* stream) {
+                        float alpha, int splitk, float* slabs, float* stat_part, void* stream, int* route_out = nullptr) {
     const int esz = dtype == P2P_BF16 ? 2 : 4;
     IgemmArgs a;
     a.C = C; a.ncols = ncols; a.w_rows = w_rows;
@@ -887,6 +920,10 @@ static int igemm_common(int op, int stride, int dtype, int N, int LH, int LW, in
         a.stat_rows = hw < bm ? hw : bm;
         a.stat_slots = slots;
     }
+    if (route_out) {        // the host query: the launcher's own decision on the launcher's own arguments, nothing started
+        *route_out = igemm_route_code(igemm_route(a, esz, !pow2, (unsigned)(phases * a.splitk)), a.w_major);
+        return 0;
+    }
     if (pow2) { P2P_DISPATCH_DTYPE(dtype, return (igemm_launch<T, false>(a, phases, vepi, st))); }
     else { P2P_DISPATCH_DTYPE(dtype, return (igemm_launch<T, true>(a, phases, vepi, st))); }
 }
@@ -942,4 +979,30 @@ extern "C" int p2p_igemm_edge(int op, int stride, int dtype, int N, int LH, int 
     P2P_REQUIRE(N > 0 && LH > 0 && LW > 0 && cin_pad > 0, "p2p_igemm_edge: bad shape");
     P2P_REQUIRE(in && out && in->ptr && out->ptr && w, "p2p_igemm_edge: null pointer");
     return igemm_common(op, stride, dtype, N, LH, LW, cin_pad, ncols, w_rows, in, out, w, bias, act, alpha, 1, nullptr, nullptr, stream);
+}
+
+// ---- host queries: the instantiation p2p_igemm / p2p_igemm_edge would start for these arguments (nothing is launched; the views
+// need their geometry only, and any 16-byte aligned non-null address) -----------------------------------------------------------------
+static const uintptr_t kRouteDummy = 1 << 12;
+
+extern "C" int p2p_igemm_route(int op, int dtype, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi, const p2p_tensor* lo,
+                               int splitk, int with_stats) {
+    if (!(op == P2P_OP_G || op == P2P_OP_P) || N <= 0 || LH <= 0 || LW <= 0 || Cg <= 0 || Cd <= 0 || Cg % 32 || Cd % 32 || !hi || !lo) return -1;
+    if (splitk == 1 && p2p_brig_ok(op, dtype, N, LH, LW, Cg, Cd)) return P2P_IGEMM_ROUTE_BRIG;
+    const p2p_tensor* in = op == P2P_OP_G ? hi : lo;
+    const p2p_tensor* out = op == P2P_OP_G ? lo : hi;
+    const int C = op == P2P_OP_G ? Cg : Cd, ncols = op == P2P_OP_G ? Cd : Cg;
+    int code = -1;
+    const int rc = igemm_common(op, 2, dtype, N, LH, LW, C, ncols, ncols, in, out, (const void*)kRouteDummy, nullptr, P2P_ACT_NONE, 0.f, splitk,
+                                splitk > 1 ? (float*)kRouteDummy : nullptr, with_stats ? (float*)kRouteDummy : nullptr, nullptr, &code);
+    return rc ? -1 : code;
+}
+
+extern "C" int p2p_igemm_edge_route(int op, int stride, int dtype, int N, int LH, int LW, int cin_pad, int ncols, int w_rows,
+                                    const p2p_tensor* in, const p2p_tensor* out, int with_bias, int act) {
+    if (!(op == P2P_OP_G || op == P2P_OP_P) || !(stride == 1 || stride == 2) || N <= 0 || LH <= 0 || LW <= 0 || cin_pad <= 0 || !in || !out) return -1;
+    int code = -1;
+    const int rc = igemm_common(op, stride, dtype, N, LH, LW, cin_pad, ncols, w_rows, in, out, (const void*)kRouteDummy,
+                                with_bias ? (const float*)kRouteDummy : nullptr, act, 0.f, 1, nullptr, nullptr, nullptr, &code);
+    return rc ? -1 : code;
 }

@@ -1054,11 +1054,67 @@ __global__ void colsum_kernel(const float* __restrict__ part, int rows, int cols
 
 static inline int pick_cb(int C) { return C >= 64 ? 64 : (C >= 32 ? 32 : (C >= 16 ? 16 : (C >= 8 ? 8 : (C >= 4 ? 4 : (C >= 2 ? 2 : 1))))); }
 
+// The form a launch takes (P2P_NORM_* of include/p2pgan.h): decided once by norm_fwd_route / norm_bwd_route from the launch
+// arguments and the cached switches, started by the launchers, reported by p2p_norm_act_fwd_route / p2p_norm_act_bwd_route.
+struct NormRoute { int form, ppl, cg, lgG, sp, slabs; };
+
+static int norm_route_code(const NormRoute& r) {
+    int lg = 0;
+    while ((1 << lg) < r.cg) ++lg;
+    return P2P_NORM_ROUTE(r.form, r.ppl, r.slabs, lg);
+}
+
+// vec: whole 16-byte vectors everywhere; nsplit as passed (with its | 0x100 / | 0x200 flags)
+static NormRoute norm_fwd_route(int N, int HW, int C, int vn, bool vec, bool has_gamma, bool has_tail, int raw_kind, int nsplit,
+                                bool has_ws, long long ws_bytes) {
+    NormRoute r = {P2P_NORM_FORM_SCALAR, 0, 0, 0, 1, 0};
+    if (vec && HW <= 16) {
+        // small maps: lane groups with register-resident pixels (also when the conv epilogue produced statistics:
+        // recomputing them from <= 64 pixels is cheaper than pooling the slots)
+        r.form = P2P_NORM_FORM_SMALL;
+        r.slabs = raw_kind == 2;
+        small_geom(HW, r.lgG, r.ppl);
+        return r;
+    }
+    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only -- their order of sums does not depend on N,
+    // and the parity gate (tests/test_train_step_gpu.py, 1e-4 on every gradient tensor at batch 2) holds only while no ReLU gate
+    // flips against the f64 oracle: a forward pass that rounds differently by a few ulp flips one (a 1e-2 error on a weight gradient)
+    const bool legacy = nsplit > 0 && (nsplit & 0x100);
+    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
+    if (nsplit > 0) nsplit &= 0xff;
+    if (vec && has_gamma && !has_tail && nsplit >= 0 && !legacy) {
+        int ppl = 0;
+        const int rcg = norm_bwd_reg_geom(n_geom, HW, C, vn, ppl, true);
+        if (rcg) {
+            r.form = P2P_NORM_FORM_REG; r.cg = rcg; r.ppl = ppl; r.slabs = raw_kind == 2;
+            return r;
+        }
+    }
+    if (vec) {
+        int CG = C > 64 ? 64 : C;
+        while (C % CG) CG -= vn;
+        const int vpp = CG / vn;
+        if (256 % vpp == 0) {
+            const int prr = 256 / vpp;
+            int sp = nsplit < 1 ? 1 : nsplit;
+            while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;       // every split keeps all pixel lanes busy
+            r.cg = CG;
+            // statistics were produced by the conv epilogue (-nsplit slots per image in ws): apply only
+            if (nsplit < 0 && has_gamma && has_ws) { r.form = P2P_NORM_FORM_VEC3; return r; }
+            if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = has_gamma ? 1 : sp;
+            r.sp = sp;
+            r.form = (sp == 1 || !has_gamma) ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
+            return r;
+        }
+    }
+    return r;
+}
+
 static int norm_act_fwd_impl(int dtype, int N, int H, int W, int C, const void* raw, int raw_kind, int nslabs,
                              long long slab_stride, const float* gamma, const float* beta, float eps, int act,
                              float alpha, const unsigned char* mask, const p2p_tensor* out, void* raw_out,
                              float* stats, float* ws, long long ws_bytes, int nsplit, const p2p_tensor* tail, int tail_ch,
-                             void* stream) {
+                             void* stream, int* route_out = nullptr) {
     P2P_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "p2p_norm_act_fwd: bad shape");
     P2P_REQUIRE(raw && out && out->ptr, "p2p_norm_act_fwd: null pointer");
     P2P_REQUIRE(raw_kind == 1 || (raw_kind == 2 && nslabs >= 1), "p2p_norm_act_fwd: bad raw_kind/nslabs");
@@ -1077,86 +1133,66 @@ static int norm_act_fwd_impl(int dtype, int N, int H, int W, int C, const void* 
         while (C % cgt) cgt -= vn;
         P2P_REQUIRE(vec && H * W > 16 && 256 % (cgt / vn) == 0, "p2p_norm_act_fwd_tail: shape not served by the vector form");
     }
-    if (vec && H * W <= 16) {
-        // small maps: lane groups with register-resident pixels (also when the conv epilogue produced statistics:
-        // recomputing them from <= 64 pixels is cheaper than pooling the slots)
-        int lgG, ppl;
-        small_geom(H * W, lgG, ppl);
+    const NormRoute r = norm_fwd_route(N, H * W, C, vn, vec, gamma != nullptr, tail != nullptr, raw_kind, nsplit, ws != nullptr, ws_bytes);
+    if (route_out) { *route_out = norm_route_code(r); return 0; }      // the host query: nothing started
+    hipStream_t st = (hipStream_t)stream;
+    if (r.form == P2P_NORM_FORM_SMALL) {
+        const int lgG = r.lgG;
         const long long items = (long long)N * (C / vn);
         const long long threads = items << lgG;
         const dim3 grid((unsigned)((threads + 255) / 256));
-        hipStream_t st = (hipStream_t)stream;
 #define NF_SMALL2(P_, S_) norm_act_fwd_small<T, P_, S_><<<grid, 256, 0, st>>>(H * W, W, C, lgG, items, raw, raw_kind, nslabs, slab_stride, gamma, \
                                                                    beta, eps, act, alpha, mask, make_view(out), (T*)raw_out, stats)
-#define NF_SMALL(P_) do { if (raw_kind == 2) NF_SMALL2(P_, 4); else NF_SMALL2(P_, 0); } while (0)
-        if (ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(1)); }
-        else if (ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(2)); }
+#define NF_SMALL(P_) do { if (r.slabs) NF_SMALL2(P_, 4); else NF_SMALL2(P_, 0); } while (0)
+        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(1)); }
+        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(2)); }
         else { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(4)); }
 #undef NF_SMALL
 #undef NF_SMALL2
         return p2p_check_launch("p2p_norm_act_fwd");
     }
-    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only -- their order of sums does not depend on N,
-    // and the parity gate (tests/test_train_step_gpu.py, 1e-4 on every gradient tensor at batch 2) holds only while no ReLU gate
-    // flips against the f64 oracle: a forward pass that rounds differently by a few ulp flips one (a 1e-2 error on a weight gradient)
-    const bool legacy = nsplit > 0 && (nsplit & 0x100);
-    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
-    if (nsplit > 0) nsplit &= 0xff;
-    if (vec && gamma && !tail && nsplit >= 0 && !legacy) {
-        int ppl = 0;
-        const int rcg = norm_bwd_reg_geom(n_geom, H * W, C, vn, ppl, true);
-        if (rcg) {
-            hipStream_t st = (hipStream_t)stream;
-            const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
+    if (r.form == P2P_NORM_FORM_REG) {
+        const int rcg = r.cg;
+        const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
 #define NF_REG2(P_, S_) norm_act_fwd_reg<T, P_, S_><<<grid, 256, 0, st>>>(N, H * W, W, C, rcg, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, \
                                                                 mask, make_view(out), (T*)raw_out, stats)
-#define NF_REG(P_) do { if (raw_kind == 2) NF_REG2(P_, 4); else NF_REG2(P_, 0); } while (0)
-            if (ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_REG(1)); }
-            else if (ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_REG(2)); }
-            else if (ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NF_REG(4)); }
-            else { P2P_DISPATCH_DTYPE(dtype, NF_REG(8)); }
+#define NF_REG(P_) do { if (r.slabs) NF_REG2(P_, 4); else NF_REG2(P_, 0); } while (0)
+        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_REG(1)); }
+        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_REG(2)); }
+        else if (r.ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NF_REG(4)); }
+        else { P2P_DISPATCH_DTYPE(dtype, NF_REG(8)); }
 #undef NF_REG
 #undef NF_REG2
-            return p2p_check_launch("p2p_norm_act_fwd");
-        }
+        return p2p_check_launch("p2p_norm_act_fwd");
     }
-    if (vec) {
-        int CG = C > 64 ? 64 : C;
-        while (C % CG) CG -= vn;
-        int vpp = CG / vn;
-        if (256 % vpp == 0) {
-            hipStream_t st = (hipStream_t)stream;
-            const int prr = 256 / vpp;
-            int sp = nsplit < 1 ? 1 : nsplit;
-            while (sp > 1 && (H * W + sp - 1) / sp < prr) sp >>= 1;       // every split keeps all pixel lanes busy
-            if (nsplit < 0 && gamma && ws) {
-                // statistics were produced by the conv epilogue (-nsplit slots per image in ws): apply only, and the
-                // pixel range can be split freely for parallelism
-                const int nslots = -nsplit;
-                int sp2 = 1;
-                while ((long long)N * (C / CG) * sp2 < 2048 && (H * W) / (sp2 * 2) >= prr && sp2 < 64) sp2 *= 2;
-                dim3 grid3(N, C / CG, sp2);
-                P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 3><<<grid3, 256, 0, st>>>(
-                                              H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                              make_view(out), (T*)raw_out, stats, ws, nslots, tv, tvecs)));
-                return p2p_check_launch("p2p_norm_act_fwd");
-            }
-            if (!ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = gamma ? 1 : sp;
-            dim3 grid(N, C / CG, sp);
-            if (sp == 1 || !gamma) {
-                P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 0><<<grid, 256, 0, st>>>(
-                                              H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                              make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
-            } else {
-                P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 1><<<grid, 256, 0, st>>>(
-                                              H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                              make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
-                P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 2><<<grid, 256, 0, st>>>(
-                                              H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                              make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
-            }
-            return p2p_check_launch("p2p_norm_act_fwd");
+    if (r.form == P2P_NORM_FORM_VEC3) {
+        // the pixel range can be split freely for parallelism
+        const int CG = r.cg, prr = 256 / (CG / vn);
+        const int nslots = -nsplit;
+        int sp2 = 1;
+        while ((long long)N * (C / CG) * sp2 < 2048 && (H * W) / (sp2 * 2) >= prr && sp2 < 64) sp2 *= 2;
+        dim3 grid3(N, C / CG, sp2);
+        P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 3><<<grid3, 256, 0, st>>>(
+                                      H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
+                                      make_view(out), (T*)raw_out, stats, ws, nslots, tv, tvecs)));
+        return p2p_check_launch("p2p_norm_act_fwd");
+    }
+    if (r.form == P2P_NORM_FORM_VEC0 || r.form == P2P_NORM_FORM_VEC12) {
+        const int CG = r.cg;
+        dim3 grid(N, C / CG, r.sp);
+        if (r.form == P2P_NORM_FORM_VEC0) {
+            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 0><<<grid, 256, 0, st>>>(
+                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
+                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
+        } else {
+            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 1><<<grid, 256, 0, st>>>(
+                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
+                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
+            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 2><<<grid, 256, 0, st>>>(
+                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
+                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
         }
+        return p2p_check_launch("p2p_norm_act_fwd");
     }
     int CB = pick_cb(C);
     dim3 grid(N, (C + CB - 1) / CB);
@@ -1165,6 +1201,18 @@ static int norm_act_fwd_impl(int dtype, int N, int H, int W, int C, const void* 
                                   H, W, C, CB, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
                                   make_view(out), (T*)raw_out, stats)));
     return p2p_check_launch("p2p_norm_act_fwd");
+}
+
+// Host query: the form p2p_norm_act_fwd / p2p_norm_act_fwd_tail (tail non-null) would start for these arguments.  Pointers need
+// their null-ness and 16-byte alignment only; nothing is launched.  -1: the arguments are refused.
+extern "C" int p2p_norm_act_fwd_route(int dtype, int N, int H, int W, int C, const void* raw, int raw_kind, int nslabs,
+                                      long long slab_stride, const float* gamma, const float* beta, const p2p_tensor* out,
+                                      void* raw_out, float* stats, float* ws, long long ws_bytes, int nsplit,
+                                      const p2p_tensor* tail, int tail_ch) {
+    int code = -1;
+    const int rc = norm_act_fwd_impl(dtype, N, H, W, C, raw, raw_kind, nslabs, slab_stride, gamma, beta, 0.f, 0, 0.f, nullptr, out, raw_out,
+                                     stats, ws, ws_bytes, nsplit, tail, tail_ch, nullptr, &code);
+    return rc ? -1 : code;
 }
 
 extern "C" int p2p_norm_act_fwd(int dtype, int N, int H, int W, int C, const void* raw, int raw_kind, int nslabs,
@@ -1189,11 +1237,52 @@ extern "C" int p2p_norm_act_fwd_tail(int dtype, int N, int H, int W, int C, cons
                              raw_out, stats, ws, ws_bytes, nsplit, tail, tail_ch, stream);
 }
 
-extern "C" int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C, const void* raw, const float* stats,
-                                const float* gamma, const float* beta, int act, float alpha,
-                                const unsigned char* mask, const p2p_gsrc* g1, const p2p_gsrc* g2,
-                                const p2p_tensor* draw, float* dgamma_part, float* dbeta_part, float* ws,
-                                long long ws_bytes, int nsplit, void* stream) {
+static NormRoute norm_bwd_route(int N, int HW, int C, int vn, bool vec, bool g_slabs, int nsplit, bool has_ws, long long ws_bytes) {
+    NormRoute r = {P2P_NORM_FORM_SCALAR, 0, 0, 0, 1, 0};
+    if (vec && HW <= 16) {
+        r.form = P2P_NORM_FORM_SMALL;
+        r.slabs = g_slabs;
+        small_geom(HW, r.lgG, r.ppl);
+        return r;
+    }
+    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only (see norm_fwd_route)
+    const bool legacy = nsplit > 0 && (nsplit & 0x100);
+    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
+    if (nsplit > 0) nsplit &= 0xff;
+    if (vec && !legacy) {
+        int ppl = 0;
+        const int rcg = norm_bwd_reg_geom(n_geom, HW, C, vn, ppl);
+        if (rcg) {
+            r.form = P2P_NORM_FORM_REG; r.cg = rcg; r.ppl = ppl; r.slabs = g_slabs;
+            return r;
+        }
+    }
+    if (vec) {
+        int CG = C > 64 ? 64 : C;
+        while (C % CG) CG -= vn;
+        // a pixel split was asked for, but 32-channel groups alone already give >= 1024 workgroups: take those and keep
+        // the one-launch form (no second read of x and the gradient from HBM)
+        const bool narrow = nsplit > 1 && CG == 64 && C % 32 == 0 && (long long)N * (C / 32) >= 1024 && HW >= 64;
+        if (narrow) CG = 32;
+        const int vpp = CG / vn;
+        if (256 % vpp == 0) {
+            const int prr = 256 / vpp;
+            int sp = (nsplit < 1 || narrow) ? 1 : nsplit;
+            while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;
+            if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = 1;
+            r.cg = CG; r.sp = sp;
+            r.form = sp == 1 ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
+            return r;
+        }
+    }
+    return r;
+}
+
+static int norm_act_bwd_impl(int dtype, int N, int H, int W, int C, const void* raw, const float* stats,
+                             const float* gamma, const float* beta, int act, float alpha,
+                             const unsigned char* mask, const p2p_gsrc* g1, const p2p_gsrc* g2,
+                             const p2p_tensor* draw, float* dgamma_part, float* dbeta_part, float* ws,
+                             long long ws_bytes, int nsplit, void* stream, int* route_out) {
     P2P_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "p2p_norm_act_bwd: bad shape");
     P2P_REQUIRE(raw && draw && draw->ptr && g1, "p2p_norm_act_bwd: null pointer");
     P2P_REQUIRE(!gamma || (stats && beta && dgamma_part && dbeta_part), "p2p_norm_act_bwd: norm needs stats/beta/partials");
@@ -1206,74 +1295,54 @@ extern "C" int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C, const voi
     const bool vec = gamma && C % 8 == 0 && draw->ld % vn == 0 && ((uintptr_t)draw->ptr % 16) == 0 &&
                      ((uintptr_t)raw % 16) == 0 && gs_ok(g1) && gs_ok(g2);
     const bool g_slabs = (g1 && g1->kind == 2) || (g2 && g2->kind == 2);      // picks the instantiation with the f32-slab loader
-    if (vec && H * W <= 16) {
-        int lgG, ppl;
-        small_geom(H * W, lgG, ppl);
+    const NormRoute r = norm_bwd_route(N, H * W, C, vn, vec, g_slabs, nsplit, ws != nullptr, ws_bytes);
+    if (route_out) { *route_out = norm_route_code(r); return 0; }      // the host query: nothing started
+    hipStream_t st = (hipStream_t)stream;
+    if (r.form == P2P_NORM_FORM_SMALL) {
+        const int lgG = r.lgG;
         const long long items = (long long)N * (C / vn);
         const long long threads = items << lgG;
         const dim3 grid((unsigned)((threads + 255) / 256));
-        hipStream_t st = (hipStream_t)stream;
 #define NB_SMALL2(P_, S_) P2P_LAUNCH_LAST((norm_act_bwd_small<T, P_, S_>), grid, dim3(256), 0, st, H * W, W, C, lgG, items, (const T*)raw, stats, gamma, beta, act, \
                                      alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part)
-#define NB_SMALL(P_) do { if (g_slabs) NB_SMALL2(P_, 4); else NB_SMALL2(P_, 0); } while (0)
-        if (ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(1)); }
-        else if (ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(2)); }
+#define NB_SMALL(P_) do { if (r.slabs) NB_SMALL2(P_, 4); else NB_SMALL2(P_, 0); } while (0)
+        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(1)); }
+        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(2)); }
         else { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(4)); }
 #undef NB_SMALL
 #undef NB_SMALL2
         return p2p_check_launch("p2p_norm_act_bwd");
     }
-    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only (see norm_act_fwd_impl)
-    const bool legacy = nsplit > 0 && (nsplit & 0x100);
-    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
-    if (nsplit > 0) nsplit &= 0xff;
-    if (vec && !legacy) {
-        int ppl = 0;
-        const int rcg = norm_bwd_reg_geom(n_geom, H * W, C, vn, ppl);
-        if (rcg) {
-            hipStream_t st = (hipStream_t)stream;
-            const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
+    if (r.form == P2P_NORM_FORM_REG) {
+        const int rcg = r.cg;
+        const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
 #define NB_REG2(P_, S_) P2P_LAUNCH_LAST((norm_act_bwd_reg<T, P_, S_>), grid, dim3(256), 0, st, N, H * W, W, C, rcg, (const T*)raw, stats, gamma, beta, act, \
                                    alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part)
-#define NB_REG(P_) do { if (g_slabs) NB_REG2(P_, 4); else NB_REG2(P_, 0); } while (0)
-            if (ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_REG(1)); }
-            else if (ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_REG(2)); }
-            else if (ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NB_REG(4)); }
-            else { P2P_DISPATCH_DTYPE(dtype, NB_REG(8)); }
+#define NB_REG(P_) do { if (r.slabs) NB_REG2(P_, 4); else NB_REG2(P_, 0); } while (0)
+        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_REG(1)); }
+        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_REG(2)); }
+        else if (r.ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NB_REG(4)); }
+        else { P2P_DISPATCH_DTYPE(dtype, NB_REG(8)); }
 #undef NB_REG
 #undef NB_REG2
-            return p2p_check_launch("p2p_norm_act_bwd");
-        }
+        return p2p_check_launch("p2p_norm_act_bwd");
     }
-    if (vec) {
-        int CG = C > 64 ? 64 : C;
-        while (C % CG) CG -= vn;
-        // a pixel split was asked for, but 32-channel groups alone already give >= 1024 workgroups: take those and keep
-        // the one-launch form (no second read of x and the gradient from HBM)
-        const bool narrow = nsplit > 1 && CG == 64 && C % 32 == 0 && (long long)N * (C / 32) >= 1024 && H * W >= 64;
-        if (narrow) CG = 32;
-        int vpp = CG / vn;
-        if (256 % vpp == 0) {
-            hipStream_t st = (hipStream_t)stream;
-            const int prr = 256 / vpp;
-            int sp = (nsplit < 1 || narrow) ? 1 : nsplit;
-            while (sp > 1 && (H * W + sp - 1) / sp < prr) sp >>= 1;
-            if (!ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = 1;
-            dim3 grid(N, C / CG, sp);
-            if (sp == 1) {
-                P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 0>), grid, dim3(256), 0, st,
-                                                          H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                                          make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
-            } else {
-                P2P_DISPATCH_DTYPE(dtype, (norm_act_bwd_vec<T, 1><<<grid, 256, 0, st>>>(
-                                              H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                              make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws)));
-                P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 2>), grid, dim3(256), 0, st,
-                                                          H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                                          make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
-            }
-            return p2p_check_launch("p2p_norm_act_bwd");
+    if (r.form == P2P_NORM_FORM_VEC0 || r.form == P2P_NORM_FORM_VEC12) {
+        const int CG = r.cg;
+        dim3 grid(N, C / CG, r.sp);
+        if (r.form == P2P_NORM_FORM_VEC0) {
+            P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 0>), grid, dim3(256), 0, st,
+                                                      H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
+                                                      make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
+        } else {
+            P2P_DISPATCH_DTYPE(dtype, (norm_act_bwd_vec<T, 1><<<grid, 256, 0, st>>>(
+                                          H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
+                                          make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws)));
+            P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 2>), grid, dim3(256), 0, st,
+                                                      H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
+                                                      make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
         }
+        return p2p_check_launch("p2p_norm_act_bwd");
     }
     int CB = pick_cb(C);
     dim3 grid(N, (C + CB - 1) / CB);
@@ -1282,6 +1351,26 @@ extern "C" int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C, const voi
                                   H, W, C, CB, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
                                   make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part)));
     return p2p_check_launch("p2p_norm_act_bwd");
+}
+
+extern "C" int p2p_norm_act_bwd(int dtype, int N, int H, int W, int C, const void* raw, const float* stats,
+                                const float* gamma, const float* beta, int act, float alpha,
+                                const unsigned char* mask, const p2p_gsrc* g1, const p2p_gsrc* g2,
+                                const p2p_tensor* draw, float* dgamma_part, float* dbeta_part, float* ws,
+                                long long ws_bytes, int nsplit, void* stream) {
+    return norm_act_bwd_impl(dtype, N, H, W, C, raw, stats, gamma, beta, act, alpha, mask, g1, g2, draw, dgamma_part, dbeta_part, ws,
+                             ws_bytes, nsplit, stream, nullptr);
+}
+
+// Host query: the form p2p_norm_act_bwd would start for these arguments.  Pointers need their null-ness and 16-byte alignment only
+// (the gradient sources their kind, ld and coff too); nothing is launched.  -1: the arguments are refused.
+extern "C" int p2p_norm_act_bwd_route(int dtype, int N, int H, int W, int C, const void* raw, const float* stats, const float* gamma,
+                                      const float* beta, const p2p_gsrc* g1, const p2p_gsrc* g2, const p2p_tensor* draw,
+                                      float* dgamma_part, float* dbeta_part, float* ws, long long ws_bytes, int nsplit) {
+    int code = -1;
+    const int rc = norm_act_bwd_impl(dtype, N, H, W, C, raw, stats, gamma, beta, 0, 0.f, nullptr, g1, g2, draw, dgamma_part, dbeta_part, ws,
+                                     ws_bytes, nsplit, nullptr, &code);
+    return rc ? -1 : code;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -488,36 +488,48 @@ static bool wgemm_pipe_ok(const WgemmArgs& a, int esz, int msplit) {
     return hspan < 0xffffffffLL && lspan < 0xffffffffLL;
 }
 
+// The one decision of the launcher (P2P_WGEMM_ROUTE_* of include/p2pgan.h): the pipelined kernel where wgemm_pipe_ok allows it, else
+// the tile by channel counts.  Started by wgemm_launch, reported by p2p_wgemm_route.  (a.chunk must be set.)
+static int wgemm_route(const WgemmArgs& a, int esz, int msplit) {
+    const int cg = a.Cg, cd = a.Cd;
+    if (wgemm_pipe_ok(a, esz, msplit)) return P2P_WGEMM_ROUTE_PIPE;
+    if (cd > 64) return cg > 64 ? P2P_WGEMM_ROUTE_128x128 : (cg > 32 ? P2P_WGEMM_ROUTE_64x128 : P2P_WGEMM_ROUTE_32x128);
+    if (cd > 32) return cg > 32 ? P2P_WGEMM_ROUTE_64x64 : P2P_WGEMM_ROUTE_32x64;
+    return cg > 32 ? P2P_WGEMM_ROUTE_64x32 : P2P_WGEMM_ROUTE_32x32;
+}
+
+static void wgemm_set_chunk(WgemmArgs& a, int esz, int msplit) {
+    const int BK = esz == 2 ? 64 : 32;
+    a.chunk = ((a.M + msplit - 1) / msplit + BK - 1) / BK * BK;
+}
+
 template <typename T>
 static int wgemm_launch(WgemmArgs& a, int msplit, hipStream_t st) {
     constexpr int ESZ = sizeof(T);
-    constexpr int BK = ESZ == 2 ? 64 : 32;
-    a.chunk = ((a.M + msplit - 1) / msplit + BK - 1) / BK * BK;
+    wgemm_set_chunk(a, ESZ, msplit);
     const int cg = a.Cg, cd = a.Cd;
-    if (wgemm_pipe_ok(a, ESZ, msplit)) {
-        static bool attr = false;
-        if (!attr) attr = p2p_allow_lds((const void*)wgemm_pipe_kernel<4>, 160 * 1024, "wgemm_pipe_kernel");
-        dim3 grid(16 * (cg / 128), cd / 128, msplit);
-        wgemm_pipe_kernel<4><<<grid, dim3(512), 4 * 32768, st>>>(a);
-        return p2p_check_launch("p2p_wgemm");
-    }
-    if (cd > 64) {
+    switch (wgemm_route(a, ESZ, msplit)) {
+        case P2P_WGEMM_ROUTE_PIPE: {
+            static bool attr = false;
+            if (!attr) attr = p2p_allow_lds((const void*)wgemm_pipe_kernel<4>, 160 * 1024, "wgemm_pipe_kernel");
+            dim3 grid(16 * (cg / 128), cd / 128, msplit);
+            wgemm_pipe_kernel<4><<<grid, dim3(512), 4 * 32768, st>>>(a);
+            break;
+        }
         // eight waves (32x64 each) per 128x128 tile: -6.5 % against four 64x64 waves in this (unpipelined) kernel, r02
-        if (cg > 64) wgemm_go<T, 128, 128, 4, 2, 1, 2>(a, msplit, st);
-        else if (cg > 32) wgemm_go<T, 64, 128, 2, 2, 1, 2>(a, msplit, st);
-        else wgemm_go<T, 32, 128, 1, 4, 1, 1>(a, msplit, st);
-    } else if (cd > 32) {
-        if (cg > 32) wgemm_go<T, 64, 64, 2, 2, 1, 1>(a, msplit, st);
-        else wgemm_go<T, 32, 64, 1, 2, 1, 1>(a, msplit, st);
-    } else {
-        if (cg > 32) wgemm_go<T, 64, 32, 2, 1, 1, 1>(a, msplit, st);
-        else wgemm_go<T, 32, 32, 1, 1, 1, 1>(a, msplit, st);
+        case P2P_WGEMM_ROUTE_128x128: wgemm_go<T, 128, 128, 4, 2, 1, 2>(a, msplit, st); break;
+        case P2P_WGEMM_ROUTE_64x128: wgemm_go<T, 64, 128, 2, 2, 1, 2>(a, msplit, st); break;
+        case P2P_WGEMM_ROUTE_32x128: wgemm_go<T, 32, 128, 1, 4, 1, 1>(a, msplit, st); break;
+        case P2P_WGEMM_ROUTE_64x64: wgemm_go<T, 64, 64, 2, 2, 1, 1>(a, msplit, st); break;
+        case P2P_WGEMM_ROUTE_32x64: wgemm_go<T, 32, 64, 1, 2, 1, 1>(a, msplit, st); break;
+        case P2P_WGEMM_ROUTE_64x32: wgemm_go<T, 64, 32, 2, 1, 1, 1>(a, msplit, st); break;
+        default: wgemm_go<T, 32, 32, 1, 1, 1, 1>(a, msplit, st); break;
     }
     return p2p_check_launch("p2p_wgemm");
 }
 
 static int wgemm_common(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi,
-                        const p2p_tensor* lo, float* dw, int msplit, void* workspace, void* stream) {
+                        const p2p_tensor* lo, float* dw, int msplit, void* workspace, void* stream, int* route_out = nullptr) {
     P2P_REQUIRE(N > 0 && LH > 0 && LW > 0 && Cg > 0 && Cd > 0, "p2p_wgemm: bad shape");
     P2P_REQUIRE(hi && lo && hi->ptr && lo->ptr && dw, "p2p_wgemm: null pointer");
     P2P_REQUIRE(msplit >= 1 && (msplit == 1 || workspace), "p2p_wgemm: msplit > 1 needs a workspace");
@@ -535,6 +547,11 @@ static int wgemm_common(int dtype, int stride, int N, int LH, int LW, int Cg, in
     a.Cg = Cg; a.Cd = Cd; a.stride = stride;
     a.live_taps = (stride == 2 && LH == 1 && LW == 1) ? 1 : 0;
     a.part = msplit == 1 ? dw : (float*)workspace;
+    if (route_out) {        // the host query: the launcher's own decision on the launcher's own arguments, nothing started
+        wgemm_set_chunk(a, esz, msplit);
+        *route_out = wgemm_route(a, esz, msplit);
+        return 0;
+    }
     hipStream_t st = (hipStream_t)stream;
     int rc;
     P2P_DISPATCH_DTYPE(dtype, rc = wgemm_launch<T>(a, msplit, st));
@@ -559,4 +576,15 @@ extern "C" int p2p_wgemm_edge(int dtype, int stride, int N, int LH, int LW, int 
                               const p2p_tensor* lo, float* dw, int msplit, void* workspace, void* stream) {
     P2P_REQUIRE(stride == 1 || stride == 2, "p2p_wgemm_edge: stride must be 1 or 2");
     return wgemm_common(dtype, stride, N, LH, LW, Cg, Cd, hi, lo, dw, msplit, workspace, stream);
+}
+
+// Host query: the kernel p2p_wgemm (stride 2, Cg and Cd multiples of 32) / p2p_wgemm_edge would start (nothing is launched; the views
+// need their geometry only, and any 16-byte aligned non-null address).  -1: the arguments are refused.
+extern "C" int p2p_wgemm_route(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi, const p2p_tensor* lo,
+                               int msplit) {
+    if (!(stride == 1 || stride == 2) || msplit < 1) return -1;
+    int code = -1;
+    float* const dummy = (float*)(uintptr_t)(1 << 12);
+    const int rc = wgemm_common(dtype, stride, N, LH, LW, Cg, Cd, hi, lo, dummy, msplit, dummy, nullptr, &code);
+    return rc ? -1 : code;
 }

@@ -419,30 +419,51 @@ extern "C" int p2p_wgrad_small_blocks(int dtype, int stride, int N, int LH, int 
     return p.blocks + (split > 1 ? split : 0);
 }
 
+// Waves per workgroup and tile window of the launch: shared by ws_launch and p2p_wgrad_small_route
+static int ws_waves(const WsPlan& p) { return (ws_waves16() && !p.pack) ? 16 : 8; }
+static int ws_tile(const WsPlan& p) {
+    if (p.GT == 1 && p.DT == 1) return P2P_WS_TILE_1x1;
+    if (p.GT == 1 && p.DT == 2) return P2P_WS_TILE_1x2;
+    if (p.GT == 1 && p.DT == 4) return P2P_WS_TILE_1x4;
+    if (p.GT == 2 && p.DT == 1) return P2P_WS_TILE_2x1;
+    return P2P_WS_TILE_2x2;
+}
+
 template <typename T>
 static int ws_launch(WsArgs& a, int stride, const WsPlan& p, hipStream_t st) {
     dim3 grid(p.blocks, p.dwins, p.gwins);
+    const int waves = ws_waves(p);
 #define WS_GO(S_, G_, D_)                                                                                              \
     do {                                                                                                               \
         static bool done = false;                                                                                      \
         if (!done)                                                                                                     \
             done = (int)p2p_allow_lds((const void*)wgrad_small_kernel<T, S_, G_, D_, 2>, 160 * 1024, "wgrad_small_kernel") &   \
                    (int)p2p_allow_lds((const void*)wgrad_small_kernel<T, S_, G_, D_, 1>, 160 * 1024, "wgrad_small_kernel");    \
-        if (ws_waves16() && !p.pack) wgrad_small_kernel<T, S_, G_, D_, 1><<<grid, dim3(1024), p.shm, st>>>(a);         \
+        if (waves == 16) wgrad_small_kernel<T, S_, G_, D_, 1><<<grid, dim3(1024), p.shm, st>>>(a);                     \
         else wgrad_small_kernel<T, S_, G_, D_, 2><<<grid, dim3(512), p.shm, st>>>(a);                                  \
     } while (0)
 #define WS_SEL(S_)                                                                                                     \
     do {                                                                                                               \
-        if (p.GT == 1 && p.DT == 1) WS_GO(S_, 1, 1);                                                                   \
-        else if (p.GT == 1 && p.DT == 2) WS_GO(S_, 1, 2);                                                              \
-        else if (p.GT == 1 && p.DT == 4) WS_GO(S_, 1, 4);                                                              \
-        else if (p.GT == 2 && p.DT == 1) WS_GO(S_, 2, 1);                                                              \
-        else WS_GO(S_, 2, 2);                                                                                          \
+        switch (ws_tile(p)) {                                                                                          \
+            case P2P_WS_TILE_1x1: WS_GO(S_, 1, 1); break;                                                              \
+            case P2P_WS_TILE_1x2: WS_GO(S_, 1, 2); break;                                                              \
+            case P2P_WS_TILE_1x4: WS_GO(S_, 1, 4); break;                                                              \
+            case P2P_WS_TILE_2x1: WS_GO(S_, 2, 1); break;                                                              \
+            default: WS_GO(S_, 2, 2); break;                                                                           \
+        }                                                                                                              \
     } while (0)
     if (stride == 1) WS_SEL(1); else WS_SEL(2);
 #undef WS_SEL
 #undef WS_GO
     return p2p_check_launch("p2p_wgrad_small");
+}
+
+// Host query: the instantiation p2p_wgrad_small would start (P2P_WS_ROUTE of include/p2pgan.h), or -1 where it refuses the shape.
+extern "C" int p2p_wgrad_small_route(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, int hi_ld, int lo_ld) {
+    if (stride != 1 && stride != 2) return -1;
+    const WsPlan p = ws_plan(dtype, stride, N, LH, LW, Cg, Cd, hi_ld, lo_ld);
+    if (!p.ok) return -1;
+    return P2P_WS_ROUTE(stride, ws_tile(p), ws_waves(p), p.pack, (p.mh || p.ml) ? 1 : 0);
 }
 
 extern "C" int p2p_wgrad_small(int dtype, int stride, int N, int LH, int LW, int Cg, int Cd, const p2p_tensor* hi,

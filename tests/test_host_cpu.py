@@ -39,6 +39,12 @@ def test_library_exports_every_symbol_of_the_header():
     L.lib()
     assert L.lib().p2p_version() >= 1
     assert L.lib().p2p_wgemm_workspace_bytes(2, 4, 4, 64, 128, 4) == 4 * 16 * 64 * 128 * 4
+    # the route queries ("which kernel would this launch start") are host-only like the *_ok / *_slots / *_blocks queries
+    routes = [s for s in syms if s.endswith("_route")]
+    assert sorted(routes) == ["p2p_brig_route", "p2p_igemm_edge_route", "p2p_igemm_route", "p2p_norm_act_bwd_route",
+                              "p2p_norm_act_fwd_route", "p2p_wgemm_route", "p2p_wgrad_small_route"]
+    assert all(s in L.SPECIAL for s in routes)
+    assert L.lib().p2p_brig_route(L.OP_G, L.F32, 256, 16, 16, 64, 256, 0) == 0          # P2P_BRIG_ROUTE_NONE: bf16 only
 
 
 def test_parameter_layout_matches_reference_counts():

@@ -77,6 +77,13 @@ flip is beyond the case's cap, the upper side is the benchmarked batch of c2 / c
                                                                         1 / (N ...) scales only
 The flip batches of the igemm.hip, norm_act.hip sp2 and hist.hip rows were computed from the launch arguments of the census with the
 launchers' formulas; those of the wgrad_small.hip and wgemm.hip rows by hand.
+The rows brig_plan (route, cbw), igemm_bm, pipe_try, igemm_launch, igemm_go, igemm_common (w_major), norm_bwd_reg_geom and
+wgemm_pipe_ok can now be read off the library instead: p2p_igemm_route / p2p_igemm_edge_route / p2p_brig_route / p2p_wgemm_route /
+p2p_wgrad_small_route / p2p_norm_act_fwd_route / p2p_norm_act_bwd_route (include/p2pgan.h "route queries") call the launchers' own
+decision functions and return the tile, K groups, stages, block order, wave tiling and norm form of a launch;
+tests/switch_routes.routes maps a decoded launch to them, and tests/test_switch_routes_cpu.py asserts with them that every arm of
+those launchers is run by this file, by test_kernels_gpu.py or by a switch setting of tests/test_switch_routes_gpu.py.  (softmax.hip:
+the generic head IS in a recorded step once engine.use_head_fused is off -- OUT_OF_SCOPE below says where it is checked.)
 """
 import ctypes as C
 import gc
@@ -107,6 +114,10 @@ CONFIGS = [("c1", "bf16"), ("c2", "bf16"), ("c3", "bf16"), ("c4", "bf16"), ("c5"
 OUT_OF_SCOPE = {
     "p2p_event_record": "stream operation", "p2p_stream_wait_event": "stream operation", "p2p_arm_stop_event": "stream operation",
     "p2p_event_create": "stream operation", "p2p_disarm_stop_event": "stream operation",
+    # the generic indexed head (engine.use_head_fused = False, or a shape p2p_head_softmax_ok refuses; its convolution is a
+    # p2p_igemm_edge launch with a checker): against f64 in both dtypes in test_hist_indexed_gpu.py::test_softmax_cce_argmax_kernel
+    # and against the fused head at the c4 launch shape in ::test_fused_indexed_head_at_the_c4_launch_shape_against_the_generic_path
+    "p2p_softmax_cce_argmax": "generic indexed head: checked against f64 by tests/test_hist_indexed_gpu.py",
 }
 
 
@@ -206,12 +217,23 @@ def _decode_device_args(eng, tables, name, args, dec):
     return dec
 
 
-def harvest(cfg, dtype_name, fuse_adam=None):
+def _overrides(fuse):
+    """the engine attributes a step case sets (engine.SWITCHES / GATES names, "side.x" for the weight-gradient stream helper): a
+    dict, or the fuse_adam switch alone (None: bench.py's defaults)"""
+    if isinstance(fuse, dict):
+        return fuse
+    return {} if fuse is None else {"fuse_adam": fuse}
+
+
+def harvest(cfg, dtype_name, overrides=None):
     """unique launch signatures of the recorded step of one bench config or step description (_build): {signature: (name, decoded
-    args)}, and the raw count.  fuse_adam: the engine's switch if not None (bench.py runs the default)"""
+    args)}, and the raw count.  overrides: engine switch attributes to set before the first step (_overrides; bench.py runs the
+    defaults)"""
     eng, step = _build(cfg, dtype_name)
-    if fuse_adam is not None:
-        eng.fuse_adam = fuse_adam
+    for attr, value in _overrides(overrides).items():
+        holder, name = E._switch_holder(eng, attr)
+        assert hasattr(holder, name), f"the engine has no switch {attr}"
+        setattr(holder, name, value)
     try:
         for _ in range(2):         # the first step of a kind is eager, the second one is recorded (_begin_record)
             step()
@@ -1793,8 +1815,10 @@ STEP_CASES = [(c, d, None) for c, d in CONFIGS] + [("c2", "bf16", True)]
 
 def _check_step(cfg, dtype_name, fuse, label):
     """harvest the recorded step, refuse unknown entry points, re-issue every unique launch (NaN before, sentinel around, a second
-    launch bit-identical) against f64 with the per-family tolerances, print the table; returns the harvest"""
+    launch bit-identical) against f64 with the per-family tolerances, print the table; returns the harvest.  fuse: the fuse_adam
+    switch, or a dict of engine switch attributes (_overrides)"""
     uniq, names = harvest(cfg, dtype_name, fuse)
+    fuse = _overrides(fuse).get("fuse_adam")
     if fuse:
         assert "p2p_adam_prep_batched" in names, "the fused-Adam step issues no p2p_adam_prep_batched"
     unknown = sorted({n for n in names if n not in CHECKERS and n not in OUT_OF_SCOPE})
