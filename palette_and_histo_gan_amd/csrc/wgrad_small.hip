@@ -41,7 +41,24 @@ __device__ __forceinline__ void glds16s(const char* g, char* l) {
 // writes lane-linear, so the stager applies the same involution to the SOURCE chunk index.
 __device__ __forceinline__ int ws_swz(int b, int m) { return b ^ (((b >> 8) & m) << 6); }
 
-template <typename T, int S, int GT, int DT, int TPW>
+// One MFMA operand of the unpacked bf16 contraction: the two transposing reads of a 16-pixel K step (pixels xl and xl + 4 of
+// the lane, rdB bytes apart).  Inline assembly, as in igemm.hip / wgemm.hip: hipcc does not know that these reads are
+// outstanding, the loop retires them with COUNTED waits of its own (ws_lgkm_wait) and tools/exp/asm_checks.py walks the
+// emitted code for a touch of a destination before its wait.
+__device__ __forceinline__ bf16x8 ws_frag(unsigned addr, unsigned rdB) {
+    union { s16x4 h[2]; bf16x8 v; } u;
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(u.h[0]) : "v"(addr));
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(u.h[1]) : "v"(addr + rdB));
+    return u.v;
+}
+template <int N>
+__device__ __forceinline__ void ws_lgkm_wait() {
+    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// PACKED: the few-channel instantiations (pack != 0; bf16, 8 waves, 1x2 / 2x1 tiles) are compiled apart, so that the
+// unpacked ones carry none of the packed loop's state.
+template <typename T, int S, int GT, int DT, int TPW, bool PACKED = false>
 __global__ __launch_bounds__(1024 / TPW) __attribute__((amdgpu_waves_per_eu(TPW == 2 && GT * DT <= 2 ? 4 : 2)))
 void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap: two workgroups per CU (<= 128 VGPRs)
     constexpr int NTHR = 1024 / TPW;                 // TPW taps per wave: 8 waves (TPW = 2) or 16 waves (TPW = 1)
@@ -50,6 +67,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int TW = a.LW, TH = a.TH;
+    const int pack = PACKED ? a.pack : 0;
     const int RH = S * TH + 3, RW = S * TW + 3;                 // hi strip incl. halo, pixels
     const int hgB = a.hi_ld * ESZ, lgB = a.lo_ld * ESZ;         // pixel bytes in HBM (multiples of 16)
     // channel windows of this workgroup (blockIdx.y: d window, blockIdx.z: g window).  A pixel wider than the window is
@@ -80,12 +98,12 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
         const int n = strip / a.strips_per_img, y0 = (strip % a.strips_per_img) * TH;
         // ---- the hi strip (rows s*y0-1 .. , columns -1 ..) and the lo strip, 16 bytes per lane -----------------
         const int hchunks_row = hrowB >> 4, hchunks = RH * hchunks_row, hcpp = hpB >> 4;
-        if (a.pack) {
+        if (pack) {
             // Packed (few-channel) layers stage whole pixels without a swizzle: a strip row in LDS is a verbatim copy of a
             // contiguous run of HBM bytes.  Rows are dealt to the waves; the row base is wave-uniform (scalar registers) and a
             // lane only adds its 16-byte slot -- no per-slot integer divisions (they bounded these layers' staging, r03).
             constexpr int NWV = NTHR / 64;
-            const int LWq = a.pack == 2 ? TW + 3 : TW, LHq = a.pack == 2 ? TH + 3 : TH, org = a.pack == 2 ? -2 : 0;
+            const int LWq = pack == 2 ? TW + 3 : TW, LHq = pack == 2 ? TH + 3 : TH, org = pack == 2 ? -2 : 0;
             const int lcr = (LWq * lpB) >> 4;
             const char* hrow0 = a.hi + ((long long)n * a.hi_img + (long long)(S * y0 - 1) * a.hi_row - 1) * hgB;
             const char* lrow0 = a.lo + ((long long)n * a.lo_img + (long long)(y0 + org) * a.lo_row + org) * lgB;
@@ -112,7 +130,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
                 glds16s(src, hiB + cI * 16);       // wave-uniform base + lane*16
             }
         }
-        const int LWp = a.pack == 2 ? TW + 3 : TW, LHp = a.pack == 2 ? TH + 3 : TH, lo_org = a.pack == 2 ? -2 : 0;
+        const int LWp = pack == 2 ? TW + 3 : TW, LHp = pack == 2 ? TH + 3 : TH, lo_org = pack == 2 ? -2 : 0;
         const int lchunks_row = (LWp * lpB) >> 4, lchunks = LHp * lchunks_row, lcpp = lpB >> 4;
         for (int cI = wave * 64; cI < lchunks; cI += NTHR) {
             int ci = cI + lane;
@@ -126,6 +144,21 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
             }
         }
     };
+    // unpacked bf16 contraction: per-lane LDS addresses of every fragment's first read at K step 0 of buffer 0 (hi: pixel
+    // s*xl + kw of row kh, lo: pixel xl), swizzled once -- the only address registers the K loop keeps
+    unsigned hp[TPW][GT], lp[DT];
+    if constexpr (ESZ == 2 && !PACKED) {
+        const int grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
+        const int chB = (16 * (grp & 1) + 4 * p) * 2;
+        const int xl = 8 * (grp >> 1) + q;
+        const unsigned hrow0 = p2p_lds32(hiL) + ((wave * TPW) >> 2) * hrowB, lrow0 = p2p_lds32(loL);
+#pragma unroll
+        for (int t = 0; t < TPW; ++t)
+#pragma unroll
+            for (int i = 0; i < GT; ++i) hp[t][i] = hrow0 + ws_swz((S * xl + ((wave * TPW + t) & 3)) * hpB + i * 64 + chB, mh);
+#pragma unroll
+        for (int j = 0; j < DT; ++j) lp[j] = lrow0 + ws_swz(xl * lpB + j * 64 + chB, ml);
+    }
     int cur = 0;
     if ((int)blockIdx.x < a.nstrips) stage_strip(blockIdx.x, hiL, loL);
     for (int strip = blockIdx.x; strip < a.nstrips; strip += gridDim.x) {
@@ -142,7 +175,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
         } else if constexpr (ESZ == 2) {
             const int grp = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
             const int chB = (16 * (grp & 1) + 4 * p) * 2;            // byte offset of this lane's 4 channels inside a 32-channel tile
-            if (a.pack) {
+            if constexpr (PACKED) {
                 // Packed taps (8 waves): the 32 channel slots of the few-channel operand's tile are 4 taps (kw = 0..3 of
                 // kernel row kh = wave & 3) x 8 channels -- a lane's 4-channel chunk belongs to tap kw = 2 (grp & 1) + (p >> 1),
                 // channels 4 (p & 1) .., and supplies that tap's pixel address to the transposing read.  The other operand
@@ -157,7 +190,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
                         for (int rd = 0; rd < 2; ++rd) {
                             const int x = x0 + 8 * (grp >> 1) + 4 * rd + q;
                             int offh, offl;
-                            if (a.pack == 1) {       // K runs over lo pixels (yy, x); hi carries the taps
+                            if (pack == 1) {       // K runs over lo pixels (yy, x); hi carries the taps
                                 offh = ((S * yy + kh) * RW + S * x + kw) * hpB + chP;
                                 offl = (yy * TW + x) * lpB + tsel * 64 + chB;
                             } else {                 // stride 1, K runs over hi INTERIOR pixels (yy, x); lo (haloed strip) carries the taps
@@ -174,52 +207,65 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
                     }
                 }
             } else {
-            // per-lane offsets of the reads of one 16-pixel K step at x0 = 0 of a row, swizzled once: a step of 16 pixels and a
-            // row are multiples of 1024 bytes whenever a mask is set, so they do not change the swizzle bits
-            int hb[TPW][GT][2], lb[DT][2];
+                // Pipelined over the K steps of the strip (steps run along a row, then down the rows: the order every
+                // accumulator has always received them in).  A fragment's two reads sit hrd / lrd bytes apart; a K step and a
+                // row advance every lane by the same (scalar) amount, swizzled or not: a step of 16 pixels, a row and the 4
+                // pixels between the two reads are multiples of 1024 / 1024 / 512 (mask 1) or 1024 (mask 3) bytes whenever a
+                // mask is set, so they leave the swizzle bits alone.  Two fragment sets of NRD reads each alternate: the
+                // reads of step k + 1 are issued before the MFMAs of step k, every fragment has registers of its own, and
+                // s_waitcnt lgkmcnt(NRD) in front of a set's MFMAs retires that set with the other one still in flight.
+                // The sched_barriers pin the order (hipcc sank the reads next to their uses, one LDS round trip per MFMA
+                // group).  No vmcnt wait in here: the strip landed behind the vmcnt(0) + barrier above.
+                constexpr int NRD = 2 * (TPW * GT + DT);
+                static_assert(NRD <= 15, "lgkmcnt is a 4-bit counter");
+                const int nk = TH * (TW >> 4), spr = TW >> 4;
+                const unsigned hrd = 4 * S * hpB, lrd = 4 * lpB;
+                const unsigned hstep = 16 * S * hpB, lstep = 16 * lpB, hrow = S * hrowB - (spr - 1) * hstep;
+                unsigned ho = cur * buf_bytes, lo = ho;
+                int xs = 0;
+                auto load = [&](bf16x8 (&fh)[TPW][GT], bf16x8 (&fl)[DT], const bool more) {
 #pragma unroll
-            for (int rd = 0; rd < 2; ++rd) {
-                const int xl = 8 * (grp >> 1) + 4 * rd + q;
-#pragma unroll
-                for (int t = 0; t < TPW; ++t)
-#pragma unroll
-                    for (int i = 0; i < GT; ++i) hb[t][i][rd] = ws_swz((S * xl + ((wave * TPW + t) & 3)) * hpB + i * 64 + chB, mh);
-#pragma unroll
-                for (int j = 0; j < DT; ++j) lb[j][rd] = ws_swz(xl * lpB + j * 64 + chB, ml);
-            }
-            for (int yy = 0; yy < TH; ++yy) {
-                for (int x0 = 0; x0 < TW; x0 += 16) {
-                    bf16x8 bfr[DT];
-                    const int lbase = (yy * TW + x0) * lpB;
-#pragma unroll
-                    for (int j = 0; j < DT; ++j) {
-                        s16x4 r[2];
-#pragma unroll
-                        for (int rd = 0; rd < 2; ++rd)
-                            r[rd] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(loC + lbase + lb[j][rd]));
-                        union { s16x4 h[2]; bf16x8 v; } u;
-                        u.h[0] = r[0]; u.h[1] = r[1];
-                        bfr[j] = u.v;
-                    }
-#pragma unroll
-                    for (int t = 0; t < TPW; ++t) {
-                        const int tap = wave * TPW + t, kh = tap >> 2;
-                        const int hbase = (S * yy + kh) * hrowB + x0 * S * hpB;
+                    for (int t = 0; t < TPW; ++t)
 #pragma unroll
                         for (int i = 0; i < GT; ++i) {
-                            s16x4 r[2];
+                            fh[t][i] = ws_frag(hp[t][i] + ho, hrd);
+                            if (t == 0 && i == 0) {
 #pragma unroll
-                            for (int rd = 0; rd < 2; ++rd)
-                                r[rd] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(hiC + hbase + hb[t][i][rd]));
-                            union { s16x4 h[2]; bf16x8 v; } u;
-                            u.h[0] = r[0]; u.h[1] = r[1];
+                                for (int j = 0; j < DT; ++j) fl[j] = ws_frag(lp[j] + lo, lrd);
+                            }
+                        }
+                    if (more) {               // (the last prefetch re-reads its own step: valid addresses, result unused)
+                        lo += lstep;
+                        if (++xs == spr) { xs = 0; ho += hrow; } else ho += hstep;
+                    }
+                };
+                auto mma = [&](const bf16x8 (&fh)[TPW][GT], const bf16x8 (&fl)[DT]) {
+#pragma unroll
+                    for (int t = 0; t < TPW; ++t)
+#pragma unroll
+                        for (int i = 0; i < GT; ++i)
 #pragma unroll
                             for (int j = 0; j < DT; ++j)
-                                acc[t][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, bfr[j], acc[t][i][j], 0, 0, 0);
-                        }
-                    }
+                                acc[t][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[t][i], fl[j], acc[t][i][j], 0, 0, 0);
+                };
+                bf16x8 fh0[TPW][GT], fl0[DT], fh1[TPW][GT], fl1[DT];
+                load(fh0, fl0, nk > 1);
+                for (int k = 0; k + 1 < nk; k += 2) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    load(fh1, fl1, k + 2 < nk);
+                    ws_lgkm_wait<NRD>();                  // set 0 is in registers
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fh0, fl0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    load(fh0, fl0, k + 3 < nk);
+                    ws_lgkm_wait<NRD>();                  // set 1
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fh1, fl1);
                 }
-            }
+                __builtin_amdgcn_sched_barrier(0);
+                ws_lgkm_wait<0>();        // nothing may be outstanding when the registers or the strip buffer are re-used
+                __builtin_amdgcn_sched_barrier(0);
+                if (nk & 1) mma(fh0, fl0);                // nk is a power of two: a strip of a single K step
             }
         } else {
             const int kl = lane >> 5, cl = lane & 31;
@@ -253,7 +299,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
     float* outp = a.part + (long long)blockIdx.x * 16 * a.Cg * a.Cd;
     const int gwin = (hpB == hgB) ? 0 : g0, dwin = (lpB == lgB) ? 0 : d0;      // whole-pixel staging covers window 0 only
     const int h = lane >> 5;
-    if (a.pack) {
+    if (pack) {
         // D[row][col]: the packed side's index is (kw = idx >> 3, channel = idx & 7) of kernel row kh = wave & 3
         if (wave < 8) {
             const int kh = wave & 3, tsel = wave >> 2;
@@ -261,7 +307,7 @@ void wgrad_small_kernel(WsArgs a) {   // 8-wave variants with <= 2 tiles per tap
             for (int e = 0; e < 16; ++e) {
                 const int row = (e & 3) + 8 * (e >> 2) + 4 * h, col = lane & 31;
                 int tap, g, d;
-                if (a.pack == 1) { tap = kh * 4 + (row >> 3); g = row & 7; d = dwin + tsel * 32 + col; }
+                if (pack == 1) { tap = kh * 4 + (row >> 3); g = row & 7; d = dwin + tsel * 32 + col; }
                 else { tap = kh * 4 + (col >> 3); g = gwin + tsel * 32 + row; d = col & 7; }
                 if (g < a.Cg && d < a.Cd) outp[((long long)tap * a.Cg + g) * a.Cd + d] = acc[0][0][0][e];
             }
@@ -439,6 +485,15 @@ static int ws_launch(WsArgs& a, int stride, const WsPlan& p, hipStream_t st) {
         if (!done)                                                                                                     \
             done = (int)p2p_allow_lds((const void*)wgrad_small_kernel<T, S_, G_, D_, 2>, 160 * 1024, "wgrad_small_kernel") &   \
                    (int)p2p_allow_lds((const void*)wgrad_small_kernel<T, S_, G_, D_, 1>, 160 * 1024, "wgrad_small_kernel");    \
+        if constexpr (sizeof(T) == 2 && G_ * D_ == 2) {          /* the packed layers: 8 waves, 1x2 / 2x1 tiles, bf16 */         \
+            if (p.pack) {                                                                                              \
+                static bool donep = false;                                                                             \
+                if (!donep)                                                                                            \
+                    donep = p2p_allow_lds((const void*)wgrad_small_kernel<T, S_, G_, D_, 2, true>, 160 * 1024, "wgrad_small_kernel"); \
+                wgrad_small_kernel<T, S_, G_, D_, 2, true><<<grid, dim3(512), p.shm, st>>>(a);                         \
+                break;                                                                                                 \
+            }                                                                                                          \
+        }                                                                                                              \
         if (waves == 16) wgrad_small_kernel<T, S_, G_, D_, 1><<<grid, dim3(1024), p.shm, st>>>(a);                     \
         else wgrad_small_kernel<T, S_, G_, D_, 2><<<grid, dim3(512), p.shm, st>>>(a);                                  \
     } while (0)
