@@ -603,6 +603,18 @@ int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, long long n,
  * p2p_adam_flat_dev outside the range. */
 int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float* v, long long n, long long ex_lo, long long ex_hi,
                            const float* lr_t_dev, float beta1, float beta2, float eps, float gscale, void* stream);
+/* Exponential moving average e of the masters p, fused into the Adam pass.  p, m, v come out as from
+ * p2p_adam_flat_dev[_excl], bit for bit; then, per element, in f32 without contraction,
+ *     e' = e + (1 - beta_t) * (p' - e),    beta_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay,    t = (float)t_dev[0]
+ * (the Adam iteration as p2p_adam_tick left it: the kernel reads it, so a recorded or captured step serves every step number).
+ * Where p' == e, e' == e exactly.  e: n floats, 16-byte aligned like the others; the _excl form leaves [ex_lo, ex_hi) of e alone
+ * too.  p2p_ema_flat is the same update as a pass of its own over an already updated p (for p2p_adam_prep_batched steps). */
+int p2p_adam_ema_flat_dev(float* p, const float* g, float* m, float* v, float* e, long long n, const float* lr_t_dev,
+                          float beta1, float beta2, float eps, float gscale, const int* t_dev, float decay, int warmup, void* stream);
+int p2p_adam_ema_flat_dev_excl(float* p, const float* g, float* m, float* v, float* e, long long n, long long ex_lo, long long ex_hi,
+                               const float* lr_t_dev, float beta1, float beta2, float eps, float gscale, const int* t_dev, float decay,
+                               int warmup, void* stream);
+int p2p_ema_flat(float* e, const float* p, long long n, const int* t_dev, float decay, int warmup, void* stream);
 int p2p_counter_add(long long* counter_dev, long long inc, void* stream);
 /* f32 gradient sum of a GradientTape (tape.py): a network's weight gradients over several calls, the two terms of a generator
  * call's d(source).  dst = src when `first` is set (the first contribution), dst += src otherwise; n floats, 16-byte aligned,

@@ -60,6 +60,9 @@ SIGNATURES = {
     "p2p_adam_tick": [_vp, _vp, _f, _f, _f, _vp],
     "p2p_adam_flat_dev": [_vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _vp],
     "p2p_adam_flat_dev_excl": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _f, _f, _f, _f, _vp],
+    "p2p_adam_ema_flat_dev": [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _vp, _f, _i, _vp],
+    "p2p_adam_ema_flat_dev_excl": [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _f, _f, _f, _f, _vp, _f, _i, _vp],
+    "p2p_ema_flat": [_vp, _vp, _ll, _vp, _f, _i, _vp],
     "p2p_counter_add": [_vp, _ll, _vp],
     "p2p_grad_accumulate": [_vp, _vp, _ll, _i, _vp],
     "p2p_dropout_mask_dev": [_vp, _ll, _ll, _vp, _ll, _ll, _vp],

@@ -123,7 +123,8 @@ class ParamStore:
         self.grads = None                     # attached by the engine (one allocation for both networks + loss slots)
         self.m = torch.zeros(off, dtype=torch.float32, device=device)
         self.v = torch.zeros(off, dtype=torch.float32, device=device)
-        self.t = 0                            # Adam iteration count (host mirror of t_dev)
+        self.ema = None                       # moving average of params (the generator's, engine.enable_ema): same layout
+        self.t = 0                           # Adam iteration count (host mirror of t_dev)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=device)       # device-resident: graph replay advances it
         self.lr_t_dev = torch.zeros(1, dtype=torch.float32, device=device)
 

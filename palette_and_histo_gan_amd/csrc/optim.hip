@@ -53,10 +53,36 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
     p = p - lr_t * m / (sqrtf(v) + eps);
 }
 
+// Exponential moving average of the generator's masters: e' = e + (1 - beta_t) * (p' - e) with
+// beta_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay and t = the Adam iteration p2p_adam_tick left in t_dev.  Three correctly
+// rounded f32 operations per element and no contraction: a NumPy float32 restatement gives the same bits, and p' == e leaves e
+// as it is.  Every path of the three kernels that average (vector body, straddling vectors, tails) goes through here.
+struct EmaArgs { float* e; const int* t_dev; float decay; int warmup; };
+
+__device__ __forceinline__ float ema_one_minus_beta(const EmaArgs& a) {
+#pragma clang fp contract(off)
+    float beta = a.decay;
+    if (a.warmup) {
+        const float t = (float)a.t_dev[0];
+        beta = fminf(a.decay, __fdiv_rn(1.f + t, 10.f + t));
+    }
+    return 1.f - beta;
+}
+
+__device__ __forceinline__ void ema_update(float& e, float p, float omb) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float s = omb * d;
+    e = e + s;
+}
+
+template <bool EMA>
 __global__ void adam_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                      float* __restrict__ v, long long n, const float* __restrict__ lr_t_dev, float b1,
-                                     float b2, float eps, float gscale) {
+                                     float b2, float eps, float gscale, EmaArgs ema) {
     const float lr_t = lr_t_dev[0];
+    float omb = 0.f;
+    if constexpr (EMA) omb = ema_one_minus_beta(ema);
     long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     long long stride = (long long)gridDim.x * blockDim.x * 4;
     for (; i + 3 < n; i += stride) {
@@ -68,10 +94,23 @@ __global__ void adam_flat_dev_kernel(float* __restrict__ p, const float* __restr
             pi[k] = pk; mi[k] = mk; vi[k] = vk;
         }
         *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
+        if constexpr (EMA) {
+            f32x4 ei = *(const f32x4*)(ema.e + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float ek = ei[k];
+                ema_update(ek, pi[k], omb);
+                ei[k] = ek;
+            }
+            *(f32x4*)(ema.e + i) = ei;
+        }
     }
     // tail (n is padded to a multiple of 4 by the host layout, kept for safety)
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long j = n / 4 * 4; j < n; ++j) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+        for (long long j = n / 4 * 4; j < n; ++j) {
+            adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+            if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
+        }
 }
 
 extern "C" int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1, float beta2, void* stream) {
@@ -88,18 +127,40 @@ extern "C" int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, l
     long long blocks = (n / 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
-    adam_flat_dev_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps, gscale);
+    adam_flat_dev_kernel<false><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps,
+                                                                                        gscale, EmaArgs{nullptr, nullptr, 0.f, 0});
     return p2p_check_launch("p2p_adam_flat_dev");
+}
+
+// p2p_adam_flat_dev and the moving average of the same element in the same pass: the fresh p is still in registers, so the average
+// costs one read and one write of e (8 bytes per element) and no launch.  p, m, v: the instructions of p2p_adam_flat_dev.
+extern "C" int p2p_adam_ema_flat_dev(float* p, const float* g, float* m, float* v, float* e, long long n, const float* lr_t_dev,
+                                     float beta1, float beta2, float eps, float gscale, const int* t_dev, float decay, int warmup,
+                                     void* stream) {
+    P2P_REQUIRE(p && g && m && v && e && n > 0 && lr_t_dev && t_dev, "p2p_adam_ema_flat_dev: bad args");
+    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                    ((uintptr_t)e % 16) == 0,
+                "p2p_adam_ema_flat_dev: buffers must be 16-byte aligned");
+    long long blocks = (n / 4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    adam_flat_dev_kernel<true><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps,
+                                                                                       gscale, EmaArgs{e, t_dev, decay, warmup});
+    return p2p_check_launch("p2p_adam_ema_flat_dev");
 }
 
 // adam_flat_dev_kernel with a hole: elements [ex_lo, ex_hi) are neither read nor written.  The 16-byte vectors that lie wholly
 // inside the hole are taken out of the index space (every lane keeps a whole share of live vectors); a vector that straddles an
 // end of the hole is updated element by element.  The arithmetic is adam_update's, as in adam_flat_dev_kernel: bit-identical
-// outside the hole.
+// outside the hole.  EMA: the moving average of the live elements in the same pass (e has the hole too).
+template <bool EMA>
 __global__ void adam_flat_dev_excl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, long long n, long long ex_lo, long long ex_hi,
-                                          const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale) {
+                                          const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale,
+                                          EmaArgs ema) {
     const float lr_t = lr_t_dev[0];
+    float omb = 0.f;
+    if constexpr (EMA) omb = ema_one_minus_beta(ema);
     const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
     const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
     const long long live = n / 4 - hole;
@@ -116,14 +177,30 @@ __global__ void adam_flat_dev_excl_kernel(float* __restrict__ p, const float* __
                 pi[k] = pk; mi[k] = mk; vi[k] = vk;
             }
             *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
+            if constexpr (EMA) {
+                f32x4 ei = *(const f32x4*)(ema.e + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float ek = ei[k];
+                    ema_update(ek, pi[k], omb);
+                    ei[k] = ek;
+                }
+                *(f32x4*)(ema.e + i) = ei;
+            }
         } else {
             for (long long j = i; j < i + 4; ++j)
-                if (j < ex_lo || j >= ex_hi) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+                if (j < ex_lo || j >= ex_hi) {
+                    adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+                    if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
+                }
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (long long j = n / 4 * 4; j < n; ++j)
-            if (j < ex_lo || j >= ex_hi) adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+            if (j < ex_lo || j >= ex_hi) {
+                adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
+                if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
+            }
 }
 
 extern "C" int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float* v, long long n, long long ex_lo, long long ex_hi,
@@ -137,9 +214,58 @@ extern "C" int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float*
     long long blocks = (live + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
-    adam_flat_dev_excl_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1,
-                                                                                       beta2, eps, gscale);
+    adam_flat_dev_excl_kernel<false><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(
+        p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1, beta2, eps, gscale, EmaArgs{nullptr, nullptr, 0.f, 0});
     return p2p_check_launch("p2p_adam_flat_dev_excl");
+}
+
+extern "C" int p2p_adam_ema_flat_dev_excl(float* p, const float* g, float* m, float* v, float* e, long long n, long long ex_lo,
+                                          long long ex_hi, const float* lr_t_dev, float beta1, float beta2, float eps, float gscale,
+                                          const int* t_dev, float decay, int warmup, void* stream) {
+    P2P_REQUIRE(p && g && m && v && e && n > 0 && lr_t_dev && t_dev, "p2p_adam_ema_flat_dev_excl: bad args");
+    P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_adam_ema_flat_dev_excl: the excluded range must lie inside [0, n)");
+    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                    ((uintptr_t)e % 16) == 0,
+                "p2p_adam_ema_flat_dev_excl: buffers must be 16-byte aligned");
+    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
+    const long long live = n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
+    long long blocks = (live + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    adam_flat_dev_excl_kernel<true><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(
+        p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1, beta2, eps, gscale, EmaArgs{e, t_dev, decay, warmup});
+    return p2p_check_launch("p2p_adam_ema_flat_dev_excl");
+}
+
+// The moving average as a pass of its own, for the steps whose Adam runs in another kernel (p2p_adam_prep_batched): reads the
+// updated p and e, writes e.  ema_update's arithmetic: the same bits as the fused forms.
+__global__ void ema_flat_kernel(const float* __restrict__ p, long long n, EmaArgs ema) {
+    const float omb = ema_one_minus_beta(ema);
+    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    long long stride = (long long)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        const f32x4 pi = *(const f32x4*)(p + i);
+        f32x4 ei = *(const f32x4*)(ema.e + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float ek = ei[k];
+            ema_update(ek, pi[k], omb);
+            ei[k] = ek;
+        }
+        *(f32x4*)(ema.e + i) = ei;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = n / 4 * 4; j < n; ++j) ema_update(ema.e[j], p[j], omb);
+}
+
+extern "C" int p2p_ema_flat(float* e, const float* p, long long n, const int* t_dev, float decay, int warmup, void* stream) {
+    P2P_REQUIRE(e && p && n > 0 && t_dev, "p2p_ema_flat: bad args");
+    P2P_REQUIRE(((uintptr_t)e % 16) == 0 && ((uintptr_t)p % 16) == 0, "p2p_ema_flat: buffers must be 16-byte aligned");
+    long long blocks = (n / 4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    ema_flat_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, n, EmaArgs{e, t_dev, decay, warmup});
+    return p2p_check_launch("p2p_ema_flat");
 }
 
 __global__ void counter_add_kernel(long long* c, long long inc) { c[0] += inc; }

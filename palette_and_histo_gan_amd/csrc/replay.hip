@@ -53,7 +53,8 @@ constexpr Entry TABLE[] = {
     P2P_E(p2p_colsum_batched) P2P_E(p2p_bce_logits) P2P_E(p2p_bce_logits_pad8)
     P2P_E(p2p_loss_partials_sum) P2P_E(p2p_tanh_l1_fwd) P2P_E(p2p_tanh_l1_fwd_pair)
     P2P_E(p2p_tanh_l1_bwd) P2P_E(p2p_tanh_l1_bwd_pad8) P2P_E(p2p_adam_flat)
-    P2P_E(p2p_adam_tick) P2P_E(p2p_adam_flat_dev) P2P_E(p2p_adam_flat_dev_excl) P2P_E(p2p_counter_add) P2P_E(p2p_grad_accumulate)
+    P2P_E(p2p_adam_tick) P2P_E(p2p_adam_flat_dev) P2P_E(p2p_adam_flat_dev_excl) P2P_E(p2p_adam_ema_flat_dev)
+    P2P_E(p2p_adam_ema_flat_dev_excl) P2P_E(p2p_ema_flat) P2P_E(p2p_counter_add) P2P_E(p2p_grad_accumulate)
     P2P_E(p2p_dropout_mask_dev) P2P_E(p2p_weight_prep) P2P_E(p2p_weight_prep_batched)
     P2P_E(p2p_adam_prep_batched) P2P_E(p2p_pack_input) P2P_E(p2p_pack_pair)
     P2P_E(p2p_pack_pair_idx) P2P_E(p2p_pack_input_multi) P2P_E(p2p_finish_losses)

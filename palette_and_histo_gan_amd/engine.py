@@ -304,7 +304,13 @@ class Pix2PixEngine:
         # learning-rate schedule
         self._slot_lr, self._slot_b1, self._slot_b2, self._slot_eps = C.c_float(), C.c_float(), C.c_float(), C.c_float()
         self.lr, self.beta1, self.beta2, self.adam_eps = 2e-4, 0.5, 0.999, 1e-7   # pix2pix_model.py:28-29
-        self.losses = self._grad_all[self.G.numel + self.D.numel:]
+        # moving average of the generator's masters (enable_ema): G.ema is None while it is off.  The decay
+        # is a slot like lr; the warm-up flag travels by value and is part of the replay key
+        self._slot_ema, self._ema_warmup = C.c_float(0.999), 1
+        self._ema_syncs = 0             # times G.ema was written from outside an optimizer step
+        self._ema_G = self._ema_W = self._ema_table = self._ema_prepped = None      # the averaged operand copies (averaged())
+        self._averaged = False          # inside averaged(): self.G / self.W are the averaged set
+        self.losses =self._grad_all[self.G.numel + self.D.numel:]
         # per-workgroup partials of the loss kernels (include/p2pgan.h P2P_LOSS_BLOCKS): rows 0..2 BCE, row 3 L1 -- the
         # order of the loss slots, so one p2p_loss_partials_sum fills losses[0..3]; row 4 = discarded (generate())
         self.loss_part = torch.zeros(5 * 256, dtype=torch.float32, device=self.device)
@@ -351,7 +357,120 @@ class Pix2PixEngine:
 
     lr, beta1, beta2 = _slot_property("_slot_lr"), _slot_property("_slot_b1"), _slot_property("_slot_b2")
     adam_eps, seed = _slot_property("_slot_eps"), _slot_property("_slot_seed")
+    ema_decay = _slot_property("_slot_ema")
     del _slot_property
+
+    # ------------------------------------------------------------------ averaged generator
+    @property
+    def ema_enabled(self):
+        return self.G.ema is not None
+
+    def enable_ema(self, decay=0.999, warmup=True):
+        """Keeps an exponential moving average of the generator's masters in G.ema (flat f32, the layout of G.params), starting as
+        a copy of them: every optimizer step of the generator then updates it in the Adam launch itself
+        (p2p_adam_ema_flat_dev[_excl]; p2p_ema_flat behind p2p_adam_prep_batched), e += (1 - beta_t) * (p' - e) with
+        beta_t = min(decay, (1 + t) / (10 + t)) under warm-up, t = the generator's Adam iteration.  The discriminator has none."""
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"the decay of the average lies in [0, 1), got {decay}")
+        self._require_live("enable_ema")
+        self.ema_decay, self._ema_warmup = float(decay), int(bool(warmup))
+        if self.G.ema is None:
+            self.G.ema = torch.empty_like(self.G.params)
+        self._sync_ema()
+
+    def disable_ema(self):
+        self._require_live("disable_ema")
+        self.G.ema = None
+        self._ema_G = self._ema_W = self._ema_table = self._ema_prepped = None
+
+    def _sync_ema(self):
+        """e := the masters (enabling, and every write of the masters from outside an optimizer step)"""
+        self.G.ema.copy_(self.G.params)
+        self._ema_syncs += 1
+
+    def load_ema(self, values):
+        """G.ema from a flat f32 tensor of its layout (a checkpoint's)"""
+        if self.G.ema is None:
+            raise RuntimeError("averaging is off (enable_ema)")
+        self.G.ema.copy_(torch.as_tensor(values, dtype=torch.float32).reshape(-1))
+        self._ema_syncs += 1
+
+    def _require_live(self, what):
+        if self._averaged:
+            raise RuntimeError(f"{what} inside engine.averaged(): the context only serves generate / generate_indexed / a plain "
+                               f"generator call; leave it before training or writing weights")
+
+    def _prepare_averaged(self):
+        """The averaged generator's parameter view and operand copies: a second ParamStore view whose `params` is G.ema, a second
+        wn / wt / wd set per generator layer and the p2p_prep_task table that derives them -- built on first use, refreshed by one
+        p2p_weight_prep_batched launch when G.ema has changed since (every optimizer step of the generator advances G.t)."""
+        import copy
+        if self._ema_G is None or self._ema_G.params is not self.G.ema:
+            self._ema_G = copy.copy(self.G)
+            self._ema_G.params = self.G.ema
+            tdt, dev = self.tdt, self.device
+            self._ema_W = dict(self.W)
+            for (sid, name), lw in self.W.items():
+                if sid != "G":
+                    continue
+                aw = LayerW(lw.cg, lw.cd, lw.hi_pad, lw.lo_pad, lw.need_g, lw.need_p)
+                for kind in ("wt", "wn", "wd"):
+                    t = getattr(lw, kind)
+                    if t is not None:
+                        setattr(aw, kind, torch.zeros(t.numel(), dtype=tdt, device=dev))
+                self._ema_W[(sid, name)] = aw
+            live = self.G, self.W
+            self.G, self.W = self._ema_G, self._ema_W
+            try:
+                self._ema_table = self._task_table([s for sid, name in self.W if sid == "G" for s in self._copy_sets(sid, name)])
+            finally:
+                self.G, self.W = live
+            self._ema_prepped = None
+        version = (self.G.t, self._ema_syncs)
+        if self._ema_prepped != version:
+            raw, ntasks, total = self._ema_table
+            if ntasks:
+                L.call("p2p_weight_prep_batched", self.dtype, _p(raw), ntasks, total, _stream())
+            self._ema_prepped = version
+
+    def averaged(self):
+        """Context manager: inside, generate / generate_indexed / a plain generator(source, training=True) call run on the averaged
+        weights G.ema (kernels from their own operand copies; gamma, beta, bias and the f32 mode's master-as-operand from G.ema).
+        Train steps, tape calls and writes of the weights raise RuntimeError inside.  Leaving restores the live set, also after an
+        exception; the recorded steps hold the live buffers' addresses and never see the context."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            if self.G.ema is None:
+                raise RuntimeError("averaging is off (enable_ema)")
+            if self._averaged:          # nested: already there
+                yield self
+                return
+            self._prepare_averaged()
+            live = self.G, self.W
+            self.G, self.W, self._averaged = self._ema_G, self._ema_W, True
+            try:
+                yield self
+            finally:
+                (self.G, self.W), self._averaged = live, False
+        return ctx()
+
+    def _adam_flat(self, store, grads, lo, hi, ex=None):
+        """One flat Adam launch over the elements [lo, hi) of a store (ex: a hole, absolute elements), the generator's with its
+        moving average folded in while averaging is on: the same launch count either way."""
+        bufs = (_p(store.params, lo), _p(grads, lo), _p(store.m, lo), _p(store.v, lo))
+        hyper = (_p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0)
+        if store is self.G and store.ema is not None:
+            ema = (_p(store.t_dev), self._slot_ema, self._ema_warmup)
+            if ex is None:
+                L.call("p2p_adam_ema_flat_dev", *bufs, _p(store.ema, lo), hi - lo, *hyper, *ema, _stream())
+            else:
+                L.call("p2p_adam_ema_flat_dev_excl", *bufs, _p(store.ema, lo), hi - lo, ex[0] - lo, ex[1] - lo, *hyper, *ema, _stream())
+        elif ex is None:
+            L.call("p2p_adam_flat_dev", *bufs, hi - lo, *hyper, _stream())
+        else:
+            L.call("p2p_adam_flat_dev_excl", *bufs, hi - lo, ex[0] - lo, ex[1] - lo, *hyper, _stream())
 
     # ------------------------------------------------------------------ parameters
     def _init_params(self):
@@ -481,15 +600,20 @@ class Pix2PixEngine:
         L.call("p2p_adam_prep_batched", self.dtype, n_elems, _p(raw), ntasks, total, _p(store.params), _p(store.grads), _p(store.m),
                _p(store.v), _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, _stream())
 
-    def refresh_weight_copies(self, part="all", outside=True):
+    def refresh_weight_copies(self, part="all", outside=True, optimizer_step=False):
         """Re-derives the per-layer weight copies from the f32 masters; runs after every Adam step (one launch per part).
         Everything that writes the masters from outside a train step (construction, set_params / set_weights, loading weights or a
         checkpoint) ends here with outside=True: every copy is refreshed, the dead bottleneck's included, and the next fused step
         looks at that kernel's Adam state again (_elision).  Inside a fused step that elides the block its copies are left alone.
-        Code that writes G.params / G.m / G.v / G.grads directly must end here too: the engine cannot see such a write."""
+        Code that writes G.params / G.m / G.v / G.grads directly must end here too: the engine cannot see such a write.
+        With averaging on, an outside write also restarts the average from the new masters (G.ema := G.params) -- unless it is
+        an optimizer step of the engine's own (apply_adam_store), whose Adam launch has just updated the average."""
+        self._require_live("writing weights")
         self._copies_version += 1
         if outside:
             self._frozen_ok = None
+            if self.G.ema is not None and not optimizer_step:
+                self._sync_ema()
         raw, ntasks, total = self._prep_tasks(part, live=bool(self._elide))
         if ntasks:
             L.call("p2p_weight_prep_batched", self.dtype, _p(raw), ntasks, total, _stream())
@@ -531,14 +655,13 @@ class Pix2PixEngine:
         hole in the launch (g = m = v = 0 there: the plain launch leaves it bit for bit as it is, and reads and writes it)."""
         ex = self._frozen if (self._elide >= 2 and store is self.G) else None
         if ex is not None and lo <= ex[0] and ex[1] <= hi:
-            L.call("p2p_adam_flat_dev_excl", _p(store.params, lo), _p(store.grads, lo), _p(store.m, lo), _p(store.v, lo), hi - lo,
-                   ex[0] - lo, ex[1] - lo, _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+            self._adam_flat(store, store.grads, lo, hi, ex)
             return
         assert ex is None or ex[1] <= lo or hi <= ex[0], "the dead kernel straddles an Adam range"
-        L.call("p2p_adam_flat_dev", _p(store.params, lo), _p(store.grads, lo), _p(store.m, lo), _p(store.v, lo), hi - lo,
-               _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+        self._adam_flat(store, store.grads, lo, hi)
 
     def set_params(self, g_values=None, d_values=None):
+        self._require_live("set_params")
         if g_values is not None:
             self.G.load(g_values)
         if d_values is not None:
@@ -949,9 +1072,12 @@ class Pix2PixEngine:
         # the step was issued on (raw handle inside the records -- the id of the torch stream object rides along, so a recycled
         # handle value of a NEW stream does not match an old recording).  Adam's hyper-parameters and the dropout seed are NOT
         # part of the key: the records hold the address of their slots (_slot_lr ...), one recording serves every value.
+        # Averaging changes the generator's Adam entry points: None while it is off, else the warm-up flag (held by value; the
+        # decay is a slot, and the kernels read the step number from G.t_dev).
         st = torch.cuda.current_stream()
+        ema = None if self.G.ema is None else int(self._ema_warmup)
         return (kind, B, _SWITCH_VALUES(self), self.use_mfma, self.side.enabled, self.side_hist.enabled,
-                int(st.cuda_stream), int(st.stream_id), int(self._elide), None if dp is None else id(dp)) + extra
+                int(st.cuda_stream), int(st.stream_id), int(self._elide), None if dp is None else id(dp), ema) + extra
 
     def _bind_batch(self, src_t, real_t):
         """the batch tensors of this step behind the re-usable pointer slots the recorded calls hold"""
@@ -1146,6 +1272,7 @@ class Pix2PixEngine:
         """One fused train step of the communicator in self._dp: replayed where a recording with its key exists, else body() is
         issued, and recorded the second time the key is seen.  The one place that puts the elision level in force and that wraps
         the communicator of a step being recorded (_RecDP): the bodies read self._dp."""
+        self._require_live("a train step")
         dp = self._dp
         self._elide = self._elision()
         try:
@@ -1239,6 +1366,7 @@ class Pix2PixEngine:
           fake_predicted) -> (total, real, fake); both written with torch operations on the tensors they are handed (f32, NHWC).
         Returns [g_total, g_adv, g_l1, g_4th or 0, d_total, d_real, d_fake].  Slower than the fused step by the hooks' own elementwise
         kernels; single GPU, not replayed (the hooks are host code)."""
+        self._require_live("a train step")
         B = int(source.shape[0])
         P = self.plan(B)
         S, ic = self.S, self.in_ch
@@ -1436,6 +1564,7 @@ class Pix2PixEngine:
         tail of an epoch, dataset_utils.py:223 has no drop_remainder): contributes zero gradients and zero loss partials,
         issues the SAME collectives in the same order as a rank with samples -- the Hellinger scalar first (histogram model),
         then the gradient buckets, then the tail with the loss slots -- and applies the same Adam update."""
+        self._require_live("a train step")
         self._dp = dp
         self._grad_all.zero_()
         if dp is not None:
@@ -1484,6 +1613,7 @@ class Pix2PixEngine:
     def apply_adam(self, g_from=0):
         """Both optimizers step with gradients taken at the same pre-update weights (pix2pix_model.py:81-83).  `g_from`:
         first generator element not yet updated by _adam_head."""
+        self._require_live("an optimizer step")
         ticked, self._ticked = self._ticked, False      # counters already advanced by _early_side of this step
         if self.fuse_adam:
             for store in (self.G, self.D):
@@ -1499,6 +1629,10 @@ class Pix2PixEngine:
                 if hi_e > lo_e:
                     L.call("p2p_adam_flat_dev", _p(store.params, lo_e), _p(store.grads, lo_e), _p(store.m, lo_e), _p(store.v, lo_e),
                            hi_e - lo_e, _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+            if self.G.ema is not None:
+                # the tiled Adam kernels do not average: one pass of its own over the whole generator, behind all of them
+                L.call("p2p_ema_flat", _p(self.G.ema), _p(self.G.params), self.G.numel, _p(self.G.t_dev), self._slot_ema,
+                       self._ema_warmup, _stream())
             raw, ntasks, total, _ = self._adam_table("extra")
             if ntasks:
                 L.call("p2p_weight_prep_batched", self.dtype, _p(raw), ntasks, total, _stream())
@@ -1661,6 +1795,7 @@ class Pix2PixEngine:
         Unfused head, four f32 (B,S,S,256) tensors (probabilities, logits, one-hot, and the hooks' gradients): opt-in only.
         Returns [g_total, g_adv, g_l1, g_4th or 0, d_total, d_real, d_fake].  Single GPU, not replayed (the hooks are host code)."""
         assert self.head == "softmax" and self.in_ch == 1, "the RGBA models have train_step_rgba_hooked"
+        self._require_live("a train step")
         B = int(source_idx.shape[0])
         P = self.plan(B)
         S, Cn = self.S, self.out_ch
@@ -1752,7 +1887,10 @@ class Pix2PixEngine:
         src_s = torch.zeros((B, S, S, ic), dtype=torch.float32, device=self.device)
         real_s = torch.zeros((B, S, S, ic), dtype=torch.float32, device=self.device)
         # warm-up on a snapshot: allocates every buffer of the plan, loads every code object, then rolls the state back
+        self._require_live("a train step")
         snap = [(t, t.clone()) for st in (self.G, self.D) for t in (st.params, st.m, st.v, st.t_dev, st.lr_t_dev)]
+        if self.G.ema is not None:
+            snap.append((self.G.ema, self.G.ema.clone()))
         snap.append((self.mask_counter_dev, self.mask_counter_dev.clone()))
         t_host = (self.G.t, self.D.t)
         side = torch.cuda.Stream(device=self.device)
@@ -1771,6 +1909,7 @@ class Pix2PixEngine:
         self.G.t, self.D.t = t_host       # the capture pass only recorded; host mirrors advance per replay below
 
         def step(source, real):
+            self._require_live("a train step")
             src_s.copy_(torch.as_tensor(source), non_blocking=True)
             real_s.copy_(torch.as_tensor(real), non_blocking=True)
             graph.replay()
@@ -1810,6 +1949,7 @@ class Pix2PixEngine:
     # the fused step on that arena.  The fused and replayed steps keep their plans and never see an arena.
     def tape_arena(self, kind, N):
         """an arena for one tape call of network `kind` ("G" / "D") on N images: pooled, or allocated"""
+        self._require_live("a tape call")
         pool = self._arena_pool.setdefault((kind, N), [])
         if pool:
             return pool.pop()
@@ -1969,8 +2109,8 @@ class Pix2PixEngine:
         """One optimizer's step (Adam.apply_gradients of a custom train_step): the store's own t / t_dev / lr_t_dev, Keras Adam on
         its flat buffer from `grads` (f32, the store's layout), then its layers' weight copies.  apply_adam is the fused step's
         form for both networks; the dropout counter is not advanced here (a tape's generator calls advance it)."""
+        self._require_live("an optimizer step")
         store.t += 1
         L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
-        L.call("p2p_adam_flat_dev", _p(store.params), _p(grads), _p(store.m), _p(store.v), store.numel, _p(store.lr_t_dev),
-               self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
-        self.refresh_weight_copies("G" if store is self.G else "D")
+        self._adam_flat(store, grads, 0, store.numel)
+        self.refresh_weight_copies("G" if store is self.G else "D", optimizer_step=True)

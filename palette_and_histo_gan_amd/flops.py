@@ -176,6 +176,12 @@ def call_work(name, args, dtype):
         return {"flops": 0.0, "mfma": None, "bytes": 7 * 4.0 * int(args[4])}        # g, m, v, p in; m, v, p out
     if name == "p2p_adam_flat_dev_excl":      # the same streams without the excluded range
         return {"flops": 0.0, "mfma": None, "bytes": 7 * 4.0 * (int(args[4]) - (int(args[6]) - int(args[5])))}
+    if name == "p2p_adam_ema_flat_dev":       # the same plus the moving average in and out
+        return {"flops": 0.0, "mfma": None, "bytes": 9 * 4.0 * int(args[5])}
+    if name == "p2p_adam_ema_flat_dev_excl":
+        return {"flops": 0.0, "mfma": None, "bytes": 9 * 4.0 * (int(args[5]) - (int(args[7]) - int(args[6])))}
+    if name == "p2p_ema_flat":                # p, e in; e out
+        return {"flops": 0.0, "mfma": None, "bytes": 3 * 4.0 * int(args[2])}
     if name == "p2p_adam_prep_batched":       # g, m, v, theta in; m, v, theta out; two operand copies out
         return {"flops": 0.0, "mfma": None, "bytes": (7 * 4.0 + 2 * esz) * int(args[1])}
     if name == "p2p_pack_pair":

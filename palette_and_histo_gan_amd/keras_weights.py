@@ -8,6 +8,8 @@ FILE FORMAT (`*.p2pw.npz`, a plain numpy .npz -- writable from a TF process with
     generator_optimizer/iterations            int64 scalar   (Adam step count t)           } optional: present when the
     generator_optimizer/m/NNN:<name>, .../v/NNN:<name>    first / second moment, same shape   } optimizer state is exported
     discriminator_optimizer/...               likewise
+    generator_ema/NNN:<name>                  the averaged generator beside the live one    } only from a model that keeps an
+    generator_averaged                        int64 scalar 1: `generator/` HOLDS the average } average (ema_decay), on request
 
 Variable ORDER = `keras.Model.get_weights()` of the reference's functional models (networks.py:39-98): the blocks in creation
 order, inside a block the Conv kernel, then tfa InstanceNormalization's gamma, then beta; the heads contribute kernel, bias:
@@ -48,6 +50,7 @@ def _check(name, arr, shape):
 
 
 GROUPS = ("generator", "discriminator")
+EMA_GROUP = "generator_ema"          # export only: the moving average of the generator's weights (engine.enable_ema)
 
 
 def _groups(eng, which):
@@ -58,13 +61,26 @@ def _groups(eng, which):
     return [(tag, eng.G if tag == "generator" else eng.D) for tag in which]
 
 
-def export_model(model, path, with_optimizer=True, which=None):
+def export_model(model, path, with_optimizer=True, which=None, averaged=False):
     """Writes the networks named in `which` (default: generator and discriminator) and, with `with_optimizer`, their Adam
-    states of a Pix2Pix*Model / engine to `path` (.npz)."""
+    states of a Pix2Pix*Model / engine to `path` (.npz).  With averaging on (engine.enable_ema), "generator_ema" in `which` adds
+    the averaged weights beside the live ones, and averaged=True writes them AS `generator/` (plus the `generator_averaged`
+    marker): a generator for inference that every reader of the format loads.  Without either the file is what it always was."""
     eng = getattr(model, "engine", model)
     out = {"format": np.array(FORMAT)}
+    which = GROUPS if which is None else tuple(which)
+    want_ema = EMA_GROUP in which
+    which = tuple(t for t in which if t != EMA_GROUP)
+    if (want_ema or averaged) and eng.G.ema is None:
+        raise ValueError("the model keeps no averaged generator (ema_decay=None)")
+    if want_ema:
+        for i, (name, w) in enumerate(eng.G.export(eng.G.ema).items()):
+            out[f"{EMA_GROUP}/{i:03d}:{name}"] = w.astype(np.float32)
+    if averaged and "generator" in which:
+        out["generator_averaged"] = np.array(1, np.int64)
     for tag, store in _groups(eng, which):
-        for i, (name, w) in enumerate(store.export().items()):
+        weights = store.export(eng.G.ema) if averaged and tag == "generator" else store.export()
+        for i, (name, w) in enumerate(weights.items()):
             out[f"{tag}/{i:03d}:{name}"] = w.astype(np.float32)
         if with_optimizer:
             out[f"{tag}_optimizer/iterations"] = np.array(store.t, np.int64)

@@ -20,7 +20,13 @@ reference's signatures for standalone evaluation.  A SUBCLASS that overrides one
 train_step detects the override and runs the hooked step instead (hooks under torch autograd, gradients into the backward
 kernels); the palette-index model takes that path only when the subclass sets `differentiable_loss_hooks = True`, and raises
 otherwise instead of silently ignoring the override.
-Extra keyword arguments (dtype, img_size, device, data_parallel, seed) are build-added; defaults reproduce the reference.
+Extra keyword arguments (dtype, img_size, device, data_parallel, seed, ema_decay, ema_warmup) are build-added; defaults reproduce
+the reference.
+
+Averaged generator (build-added): with `ema_decay` (e.g. 0.999) the engine keeps an exponential moving average
+of the generator's weights, updated inside the Adam launch of every step.  Training is unchanged; generate(), the previews,
+report_l1 / report_fid / report_palette and save_generator() then use the averaged generator (`averaged=False` asks for the live
+one), and checkpoints carry the average.  With ema_decay=None (default) nothing changes and `averaged=True` raises ValueError.
 
 Data parallelism (build-added): with `data_parallel`, every rank agrees on the same GLOBAL batch (same
 dataset seed, same order) and works on its contiguous shard (parallel.shard_bounds).  The sprite datasets of dataset_utils
@@ -130,7 +136,7 @@ class Adam:
 
 class Pix2PixModel(S2SModel):
     def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, dtype="bf16", img_size=IMG_SIZE,
-                 device="cuda:0", data_parallel=None, seed=None):
+                 device="cuda:0", data_parallel=None, seed=None, ema_decay=None, ema_warmup=True):
         super().__init__(train_ds, test_ds, model_name, architecture_name)
         if seed is None:
             from .tf_compat import global_seed      # configuration.SEED unless the notebook's tf.random.set_seed changed it
@@ -138,6 +144,7 @@ class Pix2PixModel(S2SModel):
         self.lambda_l1 = lambda_l1
         self._dtype = {"bf16": L.BF16, "f32": L.F32}[dtype] if isinstance(dtype, str) else dtype
         self._img_size, self._device, self._seed = img_size, device, seed
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.data_parallel = data_parallel
         if data_parallel is not None and hasattr(train_ds, "set_shard"):
             train_ds.set_shard(data_parallel.rank, data_parallel.world)      # produce this rank's rows only
@@ -181,6 +188,8 @@ class Pix2PixModel(S2SModel):
         d.bind(eng, eng.D)
         go._store, do._store = eng.G, eng.D
         go._engine = do._engine = eng
+        if self.ema_decay is not None:
+            eng.enable_ema(self.ema_decay, self.ema_warmup)
         if self.data_parallel is not None:
             eng.tape_refusal = ("a GradientTape step runs on one GPU (as the hooked steps): this model trains data-parallel, "
                                 "its fused train_step issues the collectives")
@@ -204,13 +213,26 @@ class Pix2PixModel(S2SModel):
         total_loss = fake_loss + real_loss
         return total_loss, real_loss, fake_loss
 
-    def generate(self, batch, snap=None):
-        """pix2pix_model.py:58-60.  `snap` (build-added) moves every generated pixel to the nearest colour of a palette
+    def _weights_for(self, averaged):
+        """context under which a generator call runs on the weights asked for: averaged=None is the averaged generator where the
+        model keeps one and the live generator otherwise; True without an average is an error"""
+        import contextlib
+        on = self.engine.ema_enabled
+        if averaged is None:
+            averaged = on
+        if averaged and not on:
+            raise ValueError("averaged=True, but this model keeps no averaged generator (construct it with ema_decay=...)")
+        return self.engine.averaged() if averaged else contextlib.nullcontext()
+
+    def generate(self, batch, snap=None, averaged=None):
+        """pix2pix_model.py:58-60.  `averaged` (build-added): the averaged generator (default where the model has one) or the live
+        one (False).  `snap` (build-added) moves every generated pixel to the nearest colour of a palette
         (palette.snap_to_palette, f32 result, not differentiable): "target" / "source" use the palette extracted from that image
         of the batch on the device (an image with more than MAX_PALETTE_SIZE colours is returned as generated), a
         (palette (B, K, 4), sizes (B,) or None) pair is used as given; None returns the generator's output unchanged."""
         source_image, target_image = batch
-        fake_image = self.generator(source_image, training=True)
+        with self._weights_for(averaged):
+            fake_image = self.generator(source_image, training=True)
         if snap is None:
             return fake_image
         if isinstance(snap, str):
@@ -534,15 +556,16 @@ class Pix2PixIndexedModel(Pix2PixModel):
     def discriminator_loss(self, real_predicted, fake_predicted):
         return super().discriminator_loss(real_predicted, fake_predicted)
 
-    def generate(self, batch):
-        """pix2pix_model.py:283-287"""
+    def generate(self, batch, averaged=None):
+        """pix2pix_model.py:283-287 (`averaged`: as Pix2PixModel.generate)"""
         source_image = batch[0]
-        return self.engine.generate_indexed(source_image)
+        with self._weights_for(averaged):
+            return self.engine.generate_indexed(source_image)
 
     def debug_discriminator_patches(self, batch_of_one):
         """pix2pix_model.py:372-431: as the base class, on index images (the discriminator of this model sees indices)"""
         source, real = batch_of_one[0], batch_of_one[1]
-        fake = self.generate(batch_of_one)
+        fake = self.generate(batch_of_one, averaged=False)          # the live pair: the discriminator was trained against it
         out = {}
         for name, img in (("real", real), ("fake", fake)):
             logits = self.discriminator([img, source], training=True)
@@ -550,10 +573,11 @@ class Pix2PixIndexedModel(Pix2PixModel):
             out[name], out[name + "_mean"] = prob, float(prob.mean())
         return out
 
-    def generate_with_probs(self, batch):
-        """pix2pix_model.py:289-293"""
+    def generate_with_probs(self, batch, averaged=None):
+        """pix2pix_model.py:289-293 (`averaged`: as Pix2PixModel.generate)"""
         source_image = batch[0]
-        return self.engine.generate_indexed(source_image, with_probs=True)
+        with self._weights_for(averaged):
+            return self.engine.generate_indexed(source_image, with_probs=True)
 
     def train_step(self, batch, step, update_steps):
         """pix2pix_model.py:295-325"""

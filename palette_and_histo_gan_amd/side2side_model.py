@@ -99,17 +99,23 @@ class Checkpoint:
 
     def state(self):
         e = self.engine
-        return {"G": e.G.params.cpu(), "G.m": e.G.m.cpu(), "G.v": e.G.v.cpu(), "G.t": e.G.t,
-                "D": e.D.params.cpu(), "D.m": e.D.m.cpu(), "D.v": e.D.v.cpu(), "D.t": e.D.t,
-                "mask_counter": int(e.mask_counter_dev.item()), "step_count": e.step_count}
+        st = {"G": e.G.params.cpu(), "G.m": e.G.m.cpu(), "G.v": e.G.v.cpu(), "G.t": e.G.t,
+              "D": e.D.params.cpu(), "D.m": e.D.m.cpu(), "D.v": e.D.v.cpu(), "D.t": e.D.t,
+              "mask_counter": int(e.mask_counter_dev.item()), "step_count": e.step_count}
+        if e.G.ema is not None:         # the averaged generator (engine.enable_ema): only a model that keeps one writes the keys
+            st["G.ema"] = e.G.ema.cpu()
+            st["ema"] = (float(e.ema_decay), bool(e._ema_warmup))
+        return st
 
     def save(self, path):
         torch.save(self.state(), path)
         return path
 
     def restore(self, path):
-        """weights, both Adam states (moments and step counts) and the dropout counter, so that the next step is the one that
-        would have followed the save"""
+        """weights, both Adam states (moments and step counts), the dropout counter and the generator's moving average, so that
+        the next step is the one that would have followed the save.  A checkpoint without an average restarts the average of a
+        model that keeps one from the restored weights; one with an average is accepted by a model that keeps none (ignored).
+        The decay and the warm-up flag stay the model's own: the stored pair is informative."""
         ck = torch.load(path, map_location="cpu")
         e = self.engine
         for store, k in ((e.G, "G"), (e.D, "D")):
@@ -120,7 +126,9 @@ class Checkpoint:
             store.t_dev.fill_(store.t)
         e.mask_counter_dev.fill_(int(ck.get("mask_counter", 0)))
         e.step_count = int(ck.get("step_count", 0))
-        e.refresh_weight_copies()
+        e.refresh_weight_copies()           # (with averaging on: G.ema := the restored weights)
+        if e.G.ema is not None and "G.ema" in ck:
+            e.load_ema(ck["G.ema"])
         return path
 
 
@@ -331,14 +339,15 @@ class S2SModel(ABC):
         return res
 
     # -- evaluation (side2side_model.py:140-176) ---------------------------------------------------------------------------
-    def select_examples_for_evaluation(self, num_images, dataset):
+    def select_examples_for_evaluation(self, num_images, dataset, averaged=None):
         """pix2pix_model.py:112-122 / :433-452: (real_images, fake_images) of the first num_images samples, each generated as a
-        batch of one like the reference does; indexed batches are looked up in their palette (io_utils.py:96-103)."""
+        batch of one like the reference does; indexed batches are looked up in their palette (io_utils.py:96-103).  averaged:
+        handed to generate() when given (None: generate's own default, the averaged generator where the model keeps one)."""
         from . import io_utils
         real, fake = [], []
         dataset = self._whole(dataset)
         for batch in dataset.unbatch().take(num_images).batch(1):
-            out = self.generate(batch)
+            out = self.generate(batch) if averaged is None else self.generate(batch, averaged=averaged)
             host = lambda t: (t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t)))   # noqa: E731
             if len(batch) == 3:          # (source_idx, target_idx, palette)
                 pal = host(batch[2][0])
@@ -357,12 +366,19 @@ class S2SModel(ABC):
     def _model_path(self, which):
         return os.sep.join(["models", "py", which, self.architecture_name, self.model_name])
 
-    def save_generator(self):
-        """side2side_model.py:178-184: `models/py/generator/<architecture>/<model>/weights.p2pw.npz` (keras_weights.py)"""
+    def save_generator(self, averaged=None):
+        """side2side_model.py:178-184: `models/py/generator/<architecture>/<model>/weights.p2pw.npz` (keras_weights.py).  A model
+        that keeps an averaged generator writes THAT one under the usual `generator/` names (the file is a generator for
+        inference) with the `generator_averaged` marker; averaged=False writes the live weights, True without an average raises."""
         from . import keras_weights
+        on = getattr(getattr(self, "engine", None), "ema_enabled", False)
+        if averaged is None:
+            averaged = on
+        if averaged and not on:
+            raise ValueError("averaged=True, but this model keeps no averaged generator (construct it with ema_decay=...)")
         os.makedirs(self._model_path("generator"), exist_ok=True)
         return keras_weights.export_model(self, os.path.join(self._model_path("generator"), "weights.p2pw.npz"),
-                                          with_optimizer=False, which=("generator",))
+                                          with_optimizer=False, which=("generator",), averaged=averaged)
 
     def save_discriminator(self):
         """side2side_model.py:190-196"""

@@ -83,6 +83,9 @@ def main():
     ap.add_argument("--dtypes", default="f32,bf16")
     ap.add_argument("--palette", action="store_true", help="also train the four models of the palette-loss comparison")
     ap.add_argument("--snap-train", action="store_true", help="also train the four models of the train-through-the-snap comparison")
+    ap.add_argument("--ema", type=float, nargs="?", const=0.999, default=None, metavar="DECAY",
+                    help="keep an averaged generator (ema_decay, default 0.999): the curve is then the averaged generator's, and the "
+                         "end reports train / test L1 of the live and of the averaged generator")
     args = ap.parse_args()
     snap_steps = args.steps if args.steps is not None else 2520
     if args.steps is None:
@@ -97,7 +100,8 @@ def main():
         train = D.SpriteRGBADataset(tr_s, tr_t, augment=False, batch_size=4, seed=47)
         test = D.SpriteRGBADataset(te_s, te_t, augment=False, batch_size=4, seed=48)
         with contextlib.redirect_stdout(sys.stderr):
-            model = M.Pix2PixModel(train, test, "front2right", f"quality-{name}", lambda_l1=100.0, dtype=name, seed=47)
+            model = M.Pix2PixModel(train, test, "front2right", f"quality-{name}", lambda_l1=100.0, dtype=name, seed=47,
+                                   ema_decay=args.ema)
         curve = []
         orig = model.report_l1
 
@@ -114,6 +118,11 @@ def main():
         tr, te = orig(44)
         out[name] = {"l1_train": float(tr), "l1_test": float(te), "wall_s": round(wall, 1),
                      "images_per_s_incl_eval": round(args.steps * 4 / wall, 1), "l1_curve_step_train_test": curve}
+        if args.ema is not None:          # report_l1 above is the averaged generator's; the live one beside it
+            live = [float(model.evaluate_l1(*model.select_examples_for_evaluation(44, ds, averaged=False))) for ds in (train, test)]
+            out[name].update({"ema_decay": args.ema, "l1_train_averaged": float(tr), "l1_test_averaged": float(te),
+                              "l1_train_live": live[0], "l1_test_live": live[1]})
+            print(f"[{name}] live generator L1 {live[0]:.5f} / {live[1]:.5f} (train/test)", file=sys.stderr, flush=True)
         print(f"[{name}] L1 {float(tr):.5f} / {float(te):.5f} (train/test), {wall:.1f} s", file=sys.stderr, flush=True)
     if "f32" in out and "bf16" in out:
         out["bf16_vs_f32"] = {"l1_train_ratio": out["bf16"]["l1_train"] / out["f32"]["l1_train"],
