@@ -357,6 +357,8 @@ __global__ __launch_bounds__(512) void brig_kernel(BrigArgs a) {
     float* const stL = (float*)(smem + 8 * PATCH);           // [8 waves][2 image selectors][CW channels][2]
     const bool want_stats = a.stat_part != nullptr;
     float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};            // lane = channel (< CW): sums over the wave's pixels, per image selector
+    // the same sums SHIFTED by the first value the lane meets, for channels that sit many standard deviations from 0 (below)
+    float u1[2] = {0.f, 0.f}, u2[2] = {0.f, 0.f}, sh[2] = {0.f, 0.f};
     typedef __attribute__((__vector_size__(4 * sizeof(bf16_t)))) bf16_t bf16x4;
     const int ph = quarter >> 1, pw = quarter & 1;           // op P: the quarter is a sub-pixel phase
 #pragma unroll
@@ -376,14 +378,20 @@ __global__ __launch_bounds__(512) void brig_kernel(BrigArgs a) {
         if ((want_stats || a.act_out != nullptr) && lane < CW) {
             const int sel = a.lgLW == 3 ? (pbi >> 1) : 0;
             const bf16_t* col = (const bf16_t*)pL + lane;
-            float t1 = 0.f, t2 = 0.f;
+            if (pbi == 0) sh[0] = (float)col[0];
+            if (pbi == 2) sh[1] = (float)col[0];             // 8-wide maps: the wave's second image starts here
+            const float shv = sel == 0 ? sh[0] : sh[1];
+            float t1 = 0.f, t2 = 0.f, d1 = 0.f, d2 = 0.f;
 #pragma unroll
             for (int i = 0; i < 32; ++i) {
                 const float v = (float)col[i * (PROW / 2)];
                 t1 += v;
                 t2 += v * v;
+                const float d = v - shv;
+                d1 += d;
+                d2 += d * d;
             }
-            if (sel == 0) { s1[0] += t1; s2[0] += t2; } else { s1[1] += t1; s2[1] += t2; }
+            if (sel == 0) { s1[0] += t1; s2[0] += t2; u1[0] += d1; u2[0] += d2; } else { s1[1] += t1; s2[1] += t2; u1[1] += d1; u2[1] += d2; }
         }
         constexpr int LPP = CW / 8, PPS = 64 / LPP;          // lanes per pixel (16 bytes each), pixels per pass
         const int ch8 = lane & (LPP - 1);
@@ -407,11 +415,20 @@ __global__ __launch_bounds__(512) void brig_kernel(BrigArgs a) {
     }
     const bool fuse = a.act_out != nullptr;
     if (want_stats || fuse) {
+        const float cw = (float)((a.lgLW == 3 ? 2 : 4) * 32);          // pixels of an (image, channel) per wave
         if (lane < CW) {
             stL[((wave * 2 + 0) * CW + lane) * 2 + 0] = s1[0];
             stL[((wave * 2 + 0) * CW + lane) * 2 + 1] = s2[0];
             stL[((wave * 2 + 1) * CW + lane) * 2 + 0] = s1[1];
             stL[((wave * 2 + 1) * CW + lane) * 2 + 1] = s2[1];
+            // (mean, centred sum of squares) of the wave's own pixels from the shifted sums, into the head of the wave's patch
+            // (free until the fused pass refills it): [2 selectors][CW][2]
+#pragma unroll
+            for (int sl = 0; sl < 2; ++sl) {
+                const float m = u1[sl] / cw;
+                ((float*)pL)[((sl * CW + lane) * 2) + 0] = sh[sl] + m;
+                ((float*)pL)[((sl * CW + lane) * 2) + 1] = fmaxf(u2[sl] - u1[sl] * m, 0.f);
+            }
         }
         __syncthreads();
         // groups of (image, channel): 8-wide maps hold 4 images per tile (image = half * 2 + selector), wider maps one image /
@@ -435,8 +452,27 @@ __global__ __launch_bounds__(512) void brig_kernel(BrigArgs a) {
             }
             const int n = img0 + img;
             const float cnt = (float)((MODE == 1 ? 4 : 1) * a.rpt * a.LW);
-            const float mean = t1 / cnt;
-            const float m2 = fmaxf(t2 - t1 * mean, 0.f);
+            float mean = t1 / cnt;
+            float m2 = fmaxf(t2 - t1 * mean, 0.f);
+            // t2 - t1 * mean cancels all but 1 / (1 + (mean / std)^2) of t2.  Past mean / std = 8 (positive operands: a conv output
+            // 64 std from 0 put rstd 277 x outside 2^-22 * 4, tests/test_numeric_edges_gpu.py) the channel takes the shifted sums
+            // instead: the waves' (mean, centred sum of squares), equally many pixels each, pooled by the parallel-variance rule
+            // as norm_act_fwd_vec<3> pools the slots.  Below it the plain sums above stand, bit for bit what they always gave (the
+            // cancellation costs them at most 6 of their 24 bits there).
+            if (t1 * mean > 64.f * m2) {
+                const int q0 = MODE == 1 ? 0 : qd, q1 = MODE == 1 ? 3 : qd;
+                float ms = 0.f;
+                for (int hf = hf0; hf <= hf1; ++hf)
+                    for (int q4 = q0; q4 <= q1; ++q4) ms += ((const float*)(smem + (hf * 4 + q4) * PATCH))[(sel * CW + c) * 2];
+                mean = ms / (float)((hf1 - hf0 + 1) * (q1 - q0 + 1));
+                m2 = 0.f;
+                for (int hf = hf0; hf <= hf1; ++hf)
+                    for (int q4 = q0; q4 <= q1; ++q4) {
+                        const float* part = (const float*)(smem + (hf * 4 + q4) * PATCH) + (sel * CW + c) * 2;
+                        const float dm = part[0] - mean;
+                        m2 += part[1] + cw * dm * dm;
+                    }
+            }
             if (n < a.N && want_stats) {
                 const int slot = a.tiles_per_img > 1 ? tile - img0 * a.tiles_per_img : 0;
                 float* dst = a.stat_part + (((long long)n * a.stat_slots + slot) * a.ncols + n0c + ch) * 2;

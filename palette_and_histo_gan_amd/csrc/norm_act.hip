@@ -265,7 +265,12 @@ __device__ __forceinline__ void mask_vload8(const unsigned char* m, float* keep,
 // deterministic).  Three short LDS stages instead of every thread re-adding all PR rows: (1) partials to red[.][pr][CG],
 // (2) thread (q, ch) adds rows q, q+Q, ... (Q = 256 / CG, i.e. VN rows each), (3) the first CG threads add the Q
 // part-sums and publish them at red[.][256 + ch].
-template <int VN>
+// TREE: stages 2 and 3 add as balanced trees, not as running sums.  The register-resident f32 forward takes it: its narrow channel
+// groups have Q = 32 ... 64 part-sums, and that many terms of one sign added one by one carried ~6 roundings into the mean and the
+// variance -- with one pixel per thread rstd went past 2^-22 (4 + k^2) and the mean past 2^-22 max|x|
+// (tests/test_numeric_edges_gpu.py).  The two-pass workgroup forms keep the running sums: they are the f32 parity mode, whose
+// gate (tests/test_train_step_gpu.py) holds only while no ReLU input a few 1e-7 from zero changes side.
+template <int VN, bool TREE = false>
 __device__ __forceinline__ void col_reduce2(float (*red)[2048], int CG, int PR, int vid, int pr, const float* s1,
                                             const float* s2, float* t1, float* t2) {
 #pragma unroll
@@ -277,14 +282,49 @@ __device__ __forceinline__ void col_reduce2(float (*red)[2048], int CG, int PR, 
     const int Q = 256 / CG;
     const int ch = threadIdx.x % CG, q = threadIdx.x / CG;
     float a = 0.f, b = 0.f;
-    for (int i = q; i < PR; i += Q) { a += red[0][i * CG + ch]; b += red[1][i * CG + ch]; }
+    if (TREE) {
+        float ra[VN], rb[VN];                    // PR / Q = VN rows per thread
+#pragma unroll
+        for (int j = 0; j < VN; ++j) { ra[j] = red[0][(q + j * Q) * CG + ch]; rb[j] = red[1][(q + j * Q) * CG + ch]; }
+#pragma unroll
+        for (int w = 1; w < VN; w *= 2)
+#pragma unroll
+            for (int j = 0; j < VN; j += 2 * w) { ra[j] += ra[j + w]; rb[j] += rb[j + w]; }
+        a = ra[0]; b = rb[0];
+    } else {
+        for (int i = q; i < PR; i += Q) { a += red[0][i * CG + ch]; b += red[1][i * CG + ch]; }
+    }
     __syncthreads();
     red[0][q * CG + ch] = a;
     red[1][q * CG + ch] = b;
     __syncthreads();
     if (threadIdx.x < CG) {
         float ta = 0.f, tb = 0.f;
-        for (int i = 0; i < Q; ++i) { ta += red[0][i * CG + threadIdx.x]; tb += red[1][i * CG + threadIdx.x]; }
+        if (TREE) {
+            // Q = 4 ... 64 part-sums (CG = 64 ... 4): eights added pairwise, the up to eight eights as a tree (absent ones are +0)
+            float fa[8], fb[8];
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                fa[g] = 0.f; fb[g] = 0.f;
+                if (8 * g < Q) {
+                    const float* pa = &red[0][8 * g * CG + threadIdx.x];
+                    const float* pb = &red[1][8 * g * CG + threadIdx.x];
+                    fa[g] = (pa[0] + pa[CG]) + (pa[2 * CG] + pa[3 * CG]);
+                    fb[g] = (pb[0] + pb[CG]) + (pb[2 * CG] + pb[3 * CG]);
+                    if (8 * g + 4 < Q) {
+                        fa[g] += (pa[4 * CG] + pa[5 * CG]) + (pa[6 * CG] + pa[7 * CG]);
+                        fb[g] += (pb[4 * CG] + pb[5 * CG]) + (pb[6 * CG] + pb[7 * CG]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int w = 1; w < 8; w *= 2)
+#pragma unroll
+                for (int g = 0; g < 8; g += 2 * w) { fa[g] += fa[g + w]; fb[g] += fb[g + w]; }
+            ta = fa[0]; tb = fb[0];
+        } else {
+            for (int i = 0; i < Q; ++i) { ta += red[0][i * CG + threadIdx.x]; tb += red[1][i * CG + threadIdx.x]; }
+        }
         red[0][256 + threadIdx.x] = ta;
         red[1][256 + threadIdx.x] = tb;
     }
@@ -744,7 +784,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_reg(int N, int HW, int W, in
 #pragma unroll
             for (int k = 0; k < VN; ++k) { const float d = x[i][k] - sh[k]; s1[k] += d; s2[k] += d * d; }
     float t1[VN], t2[VN], mu[VN], rs[VN], ga[VN], be[VN];
-    col_reduce2<VN>(red, CG, PR, vid, pr, s1, s2, t1, t2);
+    col_reduce2<VN, VN == 4>(red, CG, PR, vid, pr, s1, s2, t1, t2);       // f32: trees (see col_reduce2); bf16 inputs leave the sums room
 #pragma unroll
     for (int k = 0; k < VN; ++k) {
         const float m = t1[k] / (float)HW;
