@@ -486,6 +486,19 @@ int p2p_soft_palette_fwd(int N, int H, int W, const float* img, const int* palet
  * the pixel's nearest slot, so they do not cancel where one colour dominates. */
 int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
                          const float* gh, const float* gm, float* dimg, void* stream);
+/* The same VJP for the loss of the fused palette step, with the upstream gradient formed in the kernel from the two histograms
+ * h_real[N][K] and h_fake[N][K] (what p2p_soft_palette_fwd wrote) instead of read from a table:
+ *   gh[n][k] = w_tv * sgn(h_fake[n][k] - h_real[n][k]) for k < sizes[n] (sgn 0 = 0), 0 beyond;   gm[n] = w_conf.
+ * Equals p2p_soft_palette_bwd handed that table bit for bit (one kernel body). */
+int p2p_soft_palette_tv_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                            const float* h_real, const float* h_fake, float w_tv, float w_conf, float* dimg, void* stream);
+/* The two loss values of B images from their soft histograms and conformances (f32, dense; K <= 256):
+ *   tv_b = 0.5 sum_{k < min(sizes[b], K)} |h_fake[b][k] - h_real[b][k]|, added in ascending k (0 for sizes[b] <= 0),
+ *   out_tv[0] = inv_batch * sum_b tv_b,   out_conf[0] = inv_batch * sum_{b: sizes[b] > 0} conf_fake[b], added in ascending b.
+ * With inv_batch = 1 / global batch a rank writes its own images' share of the two batch means: the SUM over the ranks is the
+ * global value.  One workgroup, fixed-order sums, no float atomics: bit-reproducible, and an image's term does not depend on B. */
+int p2p_palette_loss(int B, int K, const float* h_real, const float* h_fake, const float* conf_fake, const int* sizes,
+                     float inv_batch, float* out_tv, float* out_conf, void* stream);
 /* Palette of every image: q = clamp(floor((img * 0.5 + 0.5) * 255 + 0.5), 0, 255) per channel (each step rounded to f32), key =
  * r + 256 g + 65536 b + 2^24 a (unsigned); palette_out[n][0 .. sizes_out[n]) = the image's distinct keys in ascending order
  * (transparent black first), unpacked to int32 RGBA, remaining rows 0.  More than `cap` (1..256) distinct colours:
@@ -677,6 +690,10 @@ int p2p_pack_pair_idx(int dtype, int N, int H, int W, const int* source, const i
  * segmentation loss (aux_slot < 0: none); g_total = adv + lambda_l1*l1 + lambda_aux*aux. */
 int p2p_finish_losses(const float* slots, int aux_slot, int l1_slot, float lambda_l1, float lambda_aux, float* out,
                       void* stream);
+/* The same result vector for a generator loss of five terms (the fused palette step): g_total = adv + lambda_l1*l1 +
+ * lambda_aux*slots[aux_slot] + lambda_aux2*slots[aux2_slot]; out[3] = slots[aux_slot]. */
+int p2p_finish_losses2(const float* slots, int aux_slot, int aux2_slot, int l1_slot, float lambda_l1, float lambda_aux,
+                       float lambda_aux2, float* out, void* stream);
 /* view in `dtype` -> dense f32 [N][H][W][C] (for generate()/tests). */
 int p2p_unpack(int dtype, int N, int H, int W, int C, const p2p_tensor* src, float* dst, void* stream);
 

@@ -74,6 +74,7 @@ SIGNATURES = {
     "p2p_pack_pair_idx": [_i, _i, _i, _i, _vp, _vp, _TP, _TP, _TP, _TP, _vp],
     "p2p_pack_input_multi": [_i, _i, _i, _i, _i, _vp, _i, _TP, _i, _vp],
     "p2p_finish_losses": [_vp, _i, _i, _f, _f, _vp, _vp],
+    "p2p_finish_losses2": [_vp, _i, _i, _i, _f, _f, _f, _vp, _vp],
     "p2p_unpack": [_i, _i, _i, _i, _i, _TP, _vp, _vp],
     "p2p_dropout_mask": [_vp, _ll, _ll, _ll, _vp],
     "p2p_rgbuv_hist_fwd": [_i, _i, _i, _i, _TP, _vp, _vp],
@@ -90,6 +91,8 @@ SIGNATURES = {
     "p2p_rgbuv_hist_general_bwd": [_i, _i, _i, _i, _TP, _i, _i, _f, _vp, _vp, _vp],
     "p2p_soft_palette_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp],
     "p2p_soft_palette_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp],
+    "p2p_soft_palette_tv_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _f, _f, _vp, _vp],
+    "p2p_palette_loss": [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp],
     "p2p_palette_extract": [_i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "p2p_palette_snap": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "p2p_palette_project_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _vp],

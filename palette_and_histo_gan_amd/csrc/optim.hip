@@ -717,6 +717,22 @@ extern "C" int p2p_finish_losses(const float* slots, int aux_slot, int l1_slot, 
     return p2p_check_launch("p2p_finish_losses");
 }
 
+// As finish_losses_kernel for a generator loss of five terms (the fused palette step): out[3] reports the first of the two extra ones.
+__global__ void finish_losses2_kernel(const float* __restrict__ l, int aux_slot, int aux2_slot, int l1_slot, float lambda_l1,
+                                      float lambda_aux, float lambda_aux2, float* __restrict__ out) {
+    float adv = l[2], l1 = l[l1_slot], aux = l[aux_slot], aux2 = l[aux2_slot];
+    out[0] = adv + lambda_l1 * l1 + lambda_aux * aux + lambda_aux2 * aux2;
+    out[1] = adv; out[2] = l1; out[3] = aux;
+    out[4] = l[0] + l[1]; out[5] = l[0]; out[6] = l[1];
+}
+
+extern "C" int p2p_finish_losses2(const float* slots, int aux_slot, int aux2_slot, int l1_slot, float lambda_l1, float lambda_aux,
+                                  float lambda_aux2, float* out, void* stream) {
+    P2P_REQUIRE(slots && out && l1_slot >= 0 && aux_slot >= 0 && aux2_slot >= 0, "p2p_finish_losses2: bad args");
+    finish_losses2_kernel<<<1, 1, 0, (hipStream_t)stream>>>(slots, aux_slot, aux2_slot, l1_slot, lambda_l1, lambda_aux, lambda_aux2, out);
+    return p2p_check_launch("p2p_finish_losses2");
+}
+
 template <typename T>
 __global__ void unpack_kernel(int N, int H, int W, int C, TView src, float* __restrict__ dst) {
     long long total = (long long)N * H * W * C;

@@ -131,10 +131,14 @@ __global__ __launch_bounds__(PAL_THREADS) void soft_palette_finish_kernel(int HW
 // about slot r.  Where one colour dominates, a_k - E a cancels to rounding in f32; about r every term of the dominant slot is
 // exactly 0 and the rest is small times small, so no wide arithmetic is needed.  x - E c = (x - c_r) - E[c - c_r] likewise.
 //   pass 1: min_k d and its first index r;  pass 2: one exponential per pair and the ten running sums.
+// TV (p2p_soft_palette_tv_bwd): the upstream gradient of the total-variation and conformance means is formed here instead of read
+// from a table -- gh is h_fake and gm is h_real, g_k = w_tv sgn(h_fake_k - h_real_k) (sgn 0 = 0: tf.abs) and the conformance weight
+// is w_conf for every image.  Everything behind the two loads is the one body: the same f32 operations on the same values.
+template <bool TV>
 __global__ __launch_bounds__(PAL_THREADS) void soft_palette_bwd_kernel(int HW, const float* __restrict__ img, const int* __restrict__ palette,
                                                                        const int* __restrict__ sizes, int K, float nscale, float two_over_tau,
                                                                        const float* __restrict__ gh, const float* __restrict__ gm,
-                                                                       float* __restrict__ dimg) {
+                                                                       float w_tv, float w_conf, float* __restrict__ dimg) {
     __shared__ float4 c[PAL_MAX];
     __shared__ float g[PAL_MAX];
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -152,9 +156,17 @@ __global__ __launch_bounds__(PAL_THREADS) void soft_palette_bwd_kernel(int HW, c
             if (valid[j]) *(float4*)(dimg + ((long long)b * HW + pix[j]) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    for (int k = tid; k < n; k += PAL_THREADS) g[k] = gh[(long long)b * K + k];
+    for (int k = tid; k < n; k += PAL_THREADS) {
+        const long long e = (long long)b * K + k;
+        if (TV) {
+            const float d = gh[e] - gm[e];
+            g[k] = d > 0.f ? w_tv : (d < 0.f ? -w_tv : 0.f);
+        } else {
+            g[k] = gh[e];
+        }
+    }
     __syncthreads();
-    const float gmb = gm[b];
+    const float gmb = TV ? w_conf : gm[b];
     float4 x[PAL_BWD_PIX];
     float mn[PAL_BWD_PIX];
     int r[PAL_BWD_PIX];
@@ -211,6 +223,50 @@ __global__ __launch_bounds__(PAL_THREADS) void soft_palette_bwd_kernel(int HW, c
         o.z = s1 * (Eac[j].z * is - ea * (Ec[j].z * is)) + s2 * ((x[j].z - cr[j].z) - Ec[j].z * is);
         o.w = s1 * (Eac[j].w * is - ea * (Ec[j].w * is)) + s2 * ((x[j].w - cr[j].w) - Ec[j].w * is);
         *(float4*)(dimg + ((long long)b * HW + pix[j]) * 4) = o;
+    }
+}
+
+// The two loss values of a batch from its soft histograms (fused step): per image tv_b = 0.5 sum_{k < n_b} |h_fake - h_real|
+// added in ascending k, then inv_batch * sum_b tv_b and inv_batch * sum_b conf_fake_b added in ascending b (an image with n_b <= 0
+// is left out of both).  One workgroup: PAL_LOSS_IMGS images at a time, their |differences| staged through LDS with coalesced loads
+// (rows padded to 257 floats: lane j walks row j without bank conflicts), one lane per image for the sum over the slots, lane 0 for
+// the sum over the images.  Every sum has one order whatever B is: an image's term does not depend on its neighbours, two launches
+// give the same bits.
+#define PAL_LOSS_IMGS 32
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_loss_kernel(int B, int K, const float* __restrict__ h_real, const float* __restrict__ h_fake,
+                                                                   const float* __restrict__ conf_fake, const int* __restrict__ sizes,
+                                                                   float inv_batch, float* __restrict__ out_tv, float* __restrict__ out_conf) {
+    __shared__ float diff[PAL_LOSS_IMGS][PAL_MAX + 1];
+    __shared__ float tv[PAL_LOSS_IMGS], cf[PAL_LOSS_IMGS];
+    const int tid = threadIdx.x;
+    float sum_tv = 0.f, sum_cf = 0.f;                        // lane 0
+    for (int b0 = 0; b0 < B; b0 += PAL_LOSS_IMGS) {
+        const int nb = B - b0 < PAL_LOSS_IMGS ? B - b0 : PAL_LOSS_IMGS;
+        for (int i = tid; i < nb * K; i += PAL_THREADS) {
+            const int j = i / K, k = i - j * K;
+            const long long e = (long long)b0 * K + i;
+            diff[j][k] = fabsf(h_fake[e] - h_real[e]);
+        }
+        __syncthreads();
+        if (tid < nb) {
+            int n = sizes[b0 + tid];
+            n = n < 0 ? 0 : (n > K ? K : n);
+            float s = 0.f;
+            for (int k = 0; k < n; ++k) s += diff[tid][k];
+            tv[tid] = 0.5f * s;
+            cf[tid] = n > 0 ? conf_fake[b0 + tid] : 0.f;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int j = 0; j < nb; ++j) {
+                sum_tv += tv[j];
+                sum_cf += cf[j];
+            }
+    }
+    if (tid == 0) {
+        *out_tv = inv_batch * sum_tv;
+        *out_conf = inv_batch * sum_cf;
     }
 }
 
@@ -621,9 +677,28 @@ extern "C" int p2p_soft_palette_bwd(int N, int H, int W, const float* img, const
     if (pal_check("p2p_soft_palette_bwd", N, H, W, img, palette, sizes, K, tau)) return -1;
     P2P_REQUIRE(gh && gm && dimg && ((uintptr_t)dimg % 16) == 0, "p2p_soft_palette_bwd: null or unaligned pointer");
     const float nscale = (float)(-1.4426950408889634 / (double)tau);
-    soft_palette_bwd_kernel<<<dim3(pal_chunks(H, W, PAL_BWD_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
-        H * W, img, palette, sizes, K, nscale, (float)(2.0 / (double)tau), gh, gm, dimg);
+    soft_palette_bwd_kernel<false><<<dim3(pal_chunks(H, W, PAL_BWD_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
+        H * W, img, palette, sizes, K, nscale, (float)(2.0 / (double)tau), gh, gm, 0.f, 0.f, dimg);
     return p2p_check_launch("p2p_soft_palette_bwd");
+}
+
+extern "C" int p2p_soft_palette_tv_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
+                                       const float* h_real, const float* h_fake, float w_tv, float w_conf, float* dimg, void* stream) {
+    if (pal_check("p2p_soft_palette_tv_bwd", N, H, W, img, palette, sizes, K, tau)) return -1;
+    P2P_REQUIRE(h_real && h_fake && dimg && ((uintptr_t)dimg % 16) == 0, "p2p_soft_palette_tv_bwd: null or unaligned pointer");
+    const float nscale = (float)(-1.4426950408889634 / (double)tau);
+    soft_palette_bwd_kernel<true><<<dim3(pal_chunks(H, W, PAL_BWD_PIX), N), PAL_THREADS, 0, (hipStream_t)stream>>>(
+        H * W, img, palette, sizes, K, nscale, (float)(2.0 / (double)tau), h_fake, h_real, w_tv, w_conf, dimg);
+    return p2p_check_launch("p2p_soft_palette_tv_bwd");
+}
+
+extern "C" int p2p_palette_loss(int B, int K, const float* h_real, const float* h_fake, const float* conf_fake, const int* sizes,
+                                float inv_batch, float* out_tv, float* out_conf, void* stream) {
+    P2P_REQUIRE(B > 0, "p2p_palette_loss: bad batch %d", B);
+    P2P_REQUIRE(K >= 1 && K <= PAL_MAX, "p2p_palette_loss: K = %d, a palette has 1..%d slots", K, PAL_MAX);
+    P2P_REQUIRE(h_real && h_fake && conf_fake && sizes && out_tv && out_conf, "p2p_palette_loss: null pointer");
+    palette_loss_kernel<<<1, PAL_THREADS, 0, (hipStream_t)stream>>>(B, K, h_real, h_fake, conf_fake, sizes, inv_batch, out_tv, out_conf);
+    return p2p_check_launch("p2p_palette_loss");
 }
 
 extern "C" int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,

@@ -1296,20 +1296,42 @@ class Pix2PixEngine:
 
     # ------------------------------------------------------------------ train step (RGBA models)
     def train_step_rgba(self, source, real, lambda_l1, lambda_hist=None, masks=None, global_batch=None,
-                        apply_update=True, dp=None, batch_offset=0):
+                        apply_update=True, dp=None, batch_offset=0, palette=None):
         """Pix2PixModel.train_step / Pix2PixHistogramModel (pix2pix_model.py:62-89,242-250).
-        Returns a device tensor [g_total, g_adv, g_l1, g_hist, d_total, d_real, d_fake] (f32)."""
+        Returns a device tensor [g_total, g_adv, g_l1, g_hist, d_total, d_real, d_fake] (f32).
+        `palette` (build-added, not together with lambda_hist): (lambda_palette, lambda_conformance, temperature) adds
+        Pix2PixPaletteModel's two loss terms to the fused step (_palette_real_early / _palette_loss); the fourth value of the
+        result is then the palette loss."""
+        palette = self._checked_palette_terms(palette, lambda_hist)
         B = int(source.shape[0])
         P = self.plan(B)
         Bg = global_batch or B
         self._dp, self._batch_offset = dp, int(batch_offset)
         src_t, real_t = self._to_device(source, self.in_ch, B), self._to_device(real, self.in_ch, B)
         key_extra = (float(lambda_l1), None if lambda_hist is None else float(lambda_hist), Bg, int(batch_offset))
+        if palette is not None:
+            key_extra += (palette,)
         return self._run_step("rgba", key_extra, P, src_t, real_t,
-                              lambda: self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update),
-                              masks, apply_update, hist=lambda_hist is not None)
+                              lambda: self._train_step_rgba_body(P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update,
+                                                                 palette),
+                              masks, apply_update, hist=lambda_hist is not None or palette is not None)
 
-    def _train_step_rgba_body(self, P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update):
+    def _checked_palette_terms(self, palette, lambda_hist):
+        """the `palette` argument of a fused step as three floats, or None"""
+        if palette is None:
+            return None
+        if lambda_hist is not None:
+            raise ValueError("palette= and lambda_hist are mutually exclusive: a fused step carries one extra generator loss")
+        if self.head != "tanh" or self.in_ch != 4 or self.out_ch != 4:
+            raise ValueError("the palette loss is defined on RGBA images: a tanh head with four input and output channels")
+        if len(palette) != 3:
+            raise ValueError(f"palette is (lambda_palette, lambda_conformance, temperature), got {palette!r}")
+        lam_pal, lam_conf, tau = (float(x) for x in palette)
+        if not 0.0 < tau < float("inf"):
+            raise ValueError(f"the temperature must be positive and finite, got {tau}")
+        return lam_pal, lam_conf, tau
+
+    def _train_step_rgba_body(self, P, B, Bg, src_t, real_t, lambda_l1, lambda_hist, masks, apply_update, palette=None):
         S, ic = self.S, self.in_ch
         self._bind_batch(src_t, real_t)
         whole_fake = ic == 4 and self.src_ch == 8 and self.dcat_ch == 8 and self.full_pixels and self.out_ch == 4
@@ -1323,20 +1345,25 @@ class Pix2PixEngine:
             self._pack(P, real_t, P["dcat"].view(coff=0), ic, ptr=self._slot_real)
         if lambda_hist is not None:
             self._hist_real_early(P, B, real_t)
+        elif palette is not None:
+            self._palette_real_early(P, B, real_t, palette[2])
         self._early_side(P, masks, apply_update)
         self.generator_forward(P, masks)
         real_view, fake_view = P["dcat"].view(coff=0), P["dcat"].view(coff=0, n0=B)
         inv_l1 = 1.0 / (Bg * S * S * self.out_ch)
+        fake32 = NULL
         if lambda_hist is not None:
             self._hist_buffers(P, B)
+            fake32 = _p(P["fake32"])
+        elif palette is not None:
+            fake32 = _p(P["p_fake32"])
         if whole_fake:
             # whole [fake | source] pixels (the source half comes from the real half's pixel)
             L.call("p2p_tanh_l1_fwd_pair", self.dtype, B, S, S, C.byref(P["z"].view()), C.byref(real_view), C.byref(fake_view), inv_l1,
-                   _p(self.loss_part, 3 * 256), _p(P["fake32"]) if lambda_hist is not None else NULL, _stream())
+                   _p(self.loss_part, 3 * 256), fake32, _stream())
         else:
             L.call("p2p_tanh_l1_fwd", self.dtype, B, S, S, self.out_ch, C.byref(P["z"].view()), C.byref(real_view),
-                   C.byref(fake_view), inv_l1, _p(self.loss_part, 3 * 256), _p(P["fake32"]) if lambda_hist is not None else NULL,
-                   _stream())
+                   C.byref(fake_view), inv_l1, _p(self.loss_part, 3 * 256), fake32, _stream())
         g_extra = None
         if lambda_hist is not None:
             # the histogram loss only needs `fake`: its kernels (f32 MFMA, ~1.8 ms at B=256) run on the side stream,
@@ -1344,16 +1371,21 @@ class Pix2PixEngine:
             self.side_hist.fork()
             with self.side_hist.run():
                 g_extra = self._histogram_loss(P, B, Bg, lambda_hist, self._dp.allreduce_scalar_sum if self._dp is not None else None)
+        elif palette is not None:
+            # likewise the palette loss (vector-ALU kernels, no collective: both terms are per-image means)
+            self.side_hist.fork()
+            with self.side_hist.run():
+                g_extra = self._palette_loss(P, B, Bg, palette)
         self.discriminator_forward(P, 2 * B)
         self._bce_logits(P, B, Bg, P["dlg"].view())
         P["skip_g_through_d"] = False
         P["head_dbias_done"] = False
         self.discriminator_backward(P, B)
-        if lambda_hist is not None:
+        if g_extra is not None:
             self.side_hist.join()
         self._tanh_l1_bwd(P, fake_view, real_view, P["g_dcat"].gsrc(), g_extra, float(lambda_l1) * inv_l1)
         self.generator_backward(P)
-        return self._finish_step(4, self._finish_args(lambda_l1, lambda_hist), apply_update)
+        return self._finish_step(4, self._finish_args(lambda_l1, lambda_hist, palette=palette), apply_update)
 
     def train_step_rgba_hooked(self, source, real, generator_loss, discriminator_loss, masks=None, apply_update=True):
         """train_step (pix2pix_model.py:62-89) for a subclass that OVERRIDES the loss hooks (pix2pix_model.py:44-56,242-250 are the
@@ -1541,8 +1573,11 @@ class Pix2PixEngine:
         if apply_update:
             self.apply_adam(g_from=head)
 
-    def _finish_args(self, lambda_l1, lambda_hist=None, lambda_aux=None):
-        """p2p_finish_losses' (slot of the fourth generator term or -1, slot of the L1 term, weight of L1, weight of the fourth)"""
+    def _finish_args(self, lambda_l1, lambda_hist=None, lambda_aux=None, palette=None):
+        """p2p_finish_losses' (slot of the fourth generator term or -1, slot of the L1 term, weight of L1, weight of the fourth);
+        with `palette` p2p_finish_losses2' (slots of the palette, conformance and L1 terms, their three weights)"""
+        if palette is not None:
+            return 4, 5, 3, float(lambda_l1), palette[0], palette[1]
         if self.head == "softmax":
             # g_total = adv + 0 * l1 + lambda_seg * seg  (lambda_l1 is hard-wired to 0, pix2pix_model.py:263,273-278)
             return 5, 6, 0.0, float(lambda_aux or 0.0)
@@ -1555,15 +1590,18 @@ class Pix2PixEngine:
     def _write_losses(self, finish_args):
         """the result vector of a fused step from the loss slots"""
         out = self._new_out()
-        L.call("p2p_finish_losses", _p(self.losses), *finish_args, self._slot_out, _stream())
+        L.call("p2p_finish_losses2" if len(finish_args) == 6 else "p2p_finish_losses", _p(self.losses), *finish_args, self._slot_out,
+               _stream())
         self.step_count += 1
         return out[:7]
 
-    def train_step_empty(self, lambda_l1, lambda_hist=None, lambda_aux=None, dp=None, apply_update=True):
+    def train_step_empty(self, lambda_l1, lambda_hist=None, lambda_aux=None, dp=None, apply_update=True, palette=None):
         """The step of a rank whose shard of the global batch is empty (global batch smaller than the world: the ragged
         tail of an epoch, dataset_utils.py:223 has no drop_remainder): contributes zero gradients and zero loss partials,
         issues the SAME collectives in the same order as a rank with samples -- the Hellinger scalar first (histogram model),
-        then the gradient buckets, then the tail with the loss slots -- and applies the same Adam update."""
+        then the gradient buckets, then the tail with the loss slots -- and applies the same Adam update.  The palette terms
+        (`palette` as for train_step_rgba) need no collective of their own: their slots are zeroed with the gradients."""
+        palette = self._checked_palette_terms(palette, lambda_hist)
         self._require_live("a train step")
         self._dp = dp
         self._grad_all.zero_()
@@ -1578,7 +1616,7 @@ class Pix2PixEngine:
         self._reduce_tail()
         if apply_update:
             self.apply_adam()
-        return self._write_losses(self._finish_args(lambda_l1, lambda_hist, lambda_aux))
+        return self._write_losses(self._finish_args(lambda_l1, lambda_hist, lambda_aux, palette=palette))
 
     def _adam_head(self, apply_update):
         """Single-GPU steps: the main stream finishes the backward pass ~70 us before the weight-gradient stream does (the
@@ -1717,6 +1755,48 @@ class Pix2PixEngine:
             L.call("p2p_rgbuv_points", L.F32, B, S, S, C.byref(view), self.HIST_POINT_CAP, _p(P["h_points"]), _p(P["h_npoints"]), _stream())
             pts, npts = _p(P["h_points"]), _p(P["h_npoints"])
         L.call("p2p_rgbuv_hist_fwd3", L.F32, B, S, S, C.byref(view), pts, npts, self.HIST_POINT_CAP, _p(out), _p(P["h_ws"]), _stream())
+
+    # -- palette loss of the fused step: Pix2PixPaletteModel.generator_loss without a torch op between two launches
+    def _palette_buffers(self, P, B):
+        if "p_pal" in P:
+            return
+        dev, S, K = self.device, self.S, MAX_PALETTE_SIZE
+        P["p_pal"] = torch.zeros((B, K, 4), dtype=torch.int32, device=dev)
+        P["p_sizes"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        P["p_hist"] = torch.empty((2, B, K), dtype=torch.float32, device=dev)       # real, fake
+        P["p_conf"] = torch.empty((2, B), dtype=torch.float32, device=dev)
+        P["p_ws"] = torch.empty(max(int(L.lib().p2p_soft_palette_workspace_bytes(B, S, S)) // 4, 1), dtype=torch.float32, device=dev)
+        P["p_dimg"] = torch.empty(B * S * S * 4, dtype=torch.float32, device=dev)
+        P["p_fake32"] = torch.empty(B * S * S * 4, dtype=torch.float32, device=dev)   # tanh output before rounding to the activation dtype
+
+    def _palette_real_early(self, P, B, real_t, tau):
+        """palette of the REAL image and its soft histogram under it (no dependence on the generator), read from the dense f32
+        input batch: issued on the histogram stream at the start of the step, beside the generator forward."""
+        self._palette_buffers(P, B)
+        S, K = self.S, MAX_PALETTE_SIZE
+        P["h_real_src"] = real_t           # keep the batch tensor alive until the kernels have run
+        self.side_hist.fork()
+        with self.side_hist.run():
+            img = self._slot_real if real_t.data_ptr() == self._slot_real.value else _p(real_t)
+            L.call("p2p_palette_extract", B, S, S, img, K, _p(P["p_pal"]), _p(P["p_sizes"]), _stream())
+            L.call("p2p_soft_palette_fwd", B, S, S, img, _p(P["p_pal"]), _p(P["p_sizes"]), K, tau, _p(P["p_hist"][0]),
+                   _p(P["p_conf"][0]), _p(P["p_ws"]), _stream())
+
+    def _palette_loss(self, P, B, Bg, palette):
+        """lambda_palette * TV(h_real, h_fake) + lambda_conformance * mean(conformance(fake)) under the real image's palette
+        (Pix2PixPaletteModel.generator_loss).  Returns the gradient source d(both terms)/d(fake) (one f32 slab).  Both are means over
+        the GLOBAL batch of per-image values: a rank writes its images' share into loss slots 4 and 5 and scales its gradient by
+        1 / Bg -- no collective (unlike the Hellinger distance); an image with more than MAX_PALETTE_SIZE colours (size -1)
+        contributes zero to both and to the gradient."""
+        lam_pal, lam_conf, tau = palette
+        S, K = self.S, MAX_PALETTE_SIZE
+        fake, pal, sizes = _p(P["p_fake32"]), _p(P["p_pal"]), _p(P["p_sizes"])
+        h_real, h_fake, conf_fake = _p(P["p_hist"][0]), _p(P["p_hist"][1]), _p(P["p_conf"][1])
+        L.call("p2p_soft_palette_fwd", B, S, S, fake, pal, sizes, K, tau, h_fake, conf_fake, _p(P["p_ws"]), _stream())
+        L.call("p2p_palette_loss", B, K, h_real, h_fake, conf_fake, sizes, 1.0 / Bg, _p(self.losses, 4), _p(self.losses, 5), _stream())
+        L.call("p2p_soft_palette_tv_bwd", B, S, S, fake, pal, sizes, K, tau, h_real, h_fake, lam_pal * 0.5 / Bg, lam_conf / Bg,
+               _p(P["p_dimg"]), _stream())
+        return L.GSrc(P["p_dimg"].data_ptr(), 2, 1, B * S * S * 4, 4, 0)
 
     def rgbuv_histogram(self, image):
         """histogram.calculate_rgbuv_histogram (histogram.py:35-81) of a dense f32 (B,S,S,4) batch in [-1,1]:

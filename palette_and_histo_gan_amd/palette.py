@@ -5,7 +5,8 @@ histogram; DESIGN.md "palette loss" holds the definitions).
 image's pixels distribute over a palette's slots and how far they sit from them (p2p_soft_palette_fwd) and is differentiable with
 respect to the image: one torch.autograd.Function whose backward is HIP as well (p2p_soft_palette_bwd), so a loss hook of
 engine.train_step_rgba_hooked or a tf.GradientTape step written with it reaches the generator.  `palette_histogram_loss` is a
-handful of torch ops on the (B, K) result.  `snap_to_palette` is the hard counterpart (p2p_palette_snap: every pixel's nearest
+handful of torch ops on the (B, K) result.  (Pix2PixPaletteModel(fused=True) does not come through here: the fused step launches the
+same kernels plus p2p_palette_loss and p2p_soft_palette_tv_bwd from engine._palette_loss)  `snap_to_palette` is the hard counterpart (p2p_palette_snap: every pixel's nearest
 palette colour in exact integer arithmetic, per-slot counts, off-palette pixels), not differentiable, for inference
 (Pix2PixModel.generate(snap=)) and evaluation (`palette_metrics`, S2SModel.report_palette).  `project_to_palette` stands between the two: it replaces every pixel by a
 palette colour -- the soft expected colour or the snap itself -- and IS differentiable (p2p_palette_project_fwd / _bwd: the exact

@@ -393,14 +393,30 @@ class Pix2PixPaletteModel(Pix2PixAugmentedModel):
     the REAL image's palette (palette.soft_palette_histogram), and lambda_conformance * the generated pixels' mean weighted squared
     distance to that palette.  The palette is extracted on the device at every step (the dataset's augmentation changes the hues
     per batch) without a host sync; an image with more than MAX_PALETTE_SIZE colours contributes nothing to either term.
-    The class overrides the loss hook, so train_step runs engine.train_step_rgba_hooked: one GPU, not replayed."""
+    The class overrides the loss hook, so by default train_step runs engine.train_step_rgba_hooked: one GPU, not replayed.
+    `fused=True` computes the same loss inside the fused step instead (engine.train_step_rgba(palette=...): HIP only, replayed,
+    data-parallel); generator_loss then remains a standalone evaluation, as in Pix2PixHistogramModel, and a subclass
+    that overrides a loss hook has to stay with the hooked step."""
 
     def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, lambda_palette, lambda_conformance=0.0,
-                 temperature=1e-3, **kw):
+                 temperature=1e-3, fused=False, **kw):
+        self.fused = bool(fused)
+        if self.fused:
+            for hook, home in (("generator_loss", Pix2PixPaletteModel), ("discriminator_loss", Pix2PixModel)):
+                owner = next(c for c in type(self).__mro__ if hook in c.__dict__)
+                if owner is not home:
+                    raise ValueError(f"{owner.__name__}.{hook} overrides the loss, but fused=True computes {home.__name__}'s own loss "
+                                     f"in HIP kernels and never calls the hook: construct the model with fused=False (the hooked step)")
         super().__init__(train_ds, test_ds, model_name, architecture_name, lambda_l1, **kw)
         if not 0.0 < float(temperature) < float("inf"):
             raise ValueError(f"the temperature must be positive and finite, got {temperature}")
         self.lambda_palette, self.lambda_conformance, self.temperature = lambda_palette, lambda_conformance, float(temperature)
+
+    def _check_hooks(self):
+        if self.fused:          # the constructor has checked that the hooks are the class's own
+            self._custom_hooks, self._hooks_checked = False, True
+            return
+        super()._check_hooks()
 
     def generator_loss(self, fake_predicted, fake_image, real_image):
         fake = torch.as_tensor(fake_image)
@@ -417,7 +433,13 @@ class Pix2PixPaletteModel(Pix2PixAugmentedModel):
         self._check_hooks()
         source_image, real_image = batch
         (src, real), Bg, lo, dp = self._shard(batch, [source_image, real_image])
-        out = self.engine.train_step_rgba_hooked(src, real, self.generator_loss, self.discriminator_loss)
+        terms = (self.lambda_palette, self.lambda_conformance, self.temperature)
+        if not self.fused:
+            out = self.engine.train_step_rgba_hooked(src, real, self.generator_loss, self.discriminator_loss)
+        elif len(src) == 0:
+            out = self.engine.train_step_empty(self.lambda_l1, dp=dp, palette=terms)
+        else:
+            out = self.engine.train_step_rgba(src, real, self.lambda_l1, global_batch=Bg, dp=dp, batch_offset=lo, palette=terms)
         g_loss, d_loss = (out[0], out[1], out[2], out[3]), (out[4], out[5], out[6])
         self._log(g_loss, d_loss, step, update_steps)
         return g_loss, d_loss
