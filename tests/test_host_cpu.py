@@ -172,3 +172,56 @@ def test_replay_table_covers_the_int_entry_points_and_replays_host_calls():
         E.pack_replay([("p2p_png_unfilter", (1, 2, 3))])
     with pytest.raises(TypeError):
         E.pack_replay([("p2p_png_unfilter", ("text", h, rb, bpp, slot))])
+
+
+# ---------------------------------------------------------------------------------------------------------------- environment switches
+# the library's A/B switches (csrc/: each read with getenv + atoi)
+LIBRARY_SWITCHES = {"P2P_BRIG", "P2P_BRIG_CBW", "P2P_BRIG_MIN_WG", "P2P_BRIG_STAGGER", "P2P_BRIG_FUSE_NORM", "P2P_IGEMM_BIG",
+                    "P2P_IGEMM_PIPE", "P2P_IGEMM_WMAJOR", "P2P_WGEMM_PIPE", "P2P_WGEMM_PIPE_MAXWG", "P2P_WS_PACK", "P2P_WS_W16",
+                    "P2P_WS_SWIZZLE", "P2P_WS_TH_PACK", "P2P_WS_WANT_PACK", "P2P_WS_WANT", "P2P_WS_ABL", "P2P_NORM_FWD_REG",
+                    "P2P_NORM_BWD_REG", "P2P_NORM_REG_WGS"}
+
+
+def _library_switch_defaults():
+    """{environment name: default} as the kernel sources read them: `getenv("NAME") ... atoi(e) : DEFAULT` or a helper called
+    with ("NAME", DEFAULT)"""
+    csrc = os.path.join(ROOT, "palette_and_histo_gan_amd", "csrc")
+    out = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(csrc, f)).read()
+            for m in re.finditer(r'"(P2P_[A-Z0-9_]+)"', text):
+                d = re.search(r'(?:atoi\(\w+\) : |", )(\d+)', text[m.start():m.start() + 200])
+                assert d and m.group(1) not in out, (f, m.group(1))
+                out[m.group(1)] = int(d.group(1))
+    return out
+
+
+def _readme_switch_rows():
+    """{environment name: default text} of README's "Tuning / A-B switches" table"""
+    out = {}
+    for line in open(os.path.join(ROOT, "README.md")):
+        if line.startswith("| `P2P_"):
+            names_col, defaults_col = [c.strip() for c in line.split("|")[1:3]]
+            names = re.findall(r"`(P2P_[A-Z0-9_]+)`", names_col)
+            defaults = [d.strip() for d in defaults_col.split(",")] if len(names) > 1 and "," in defaults_col else [defaults_col] * len(names)
+            assert len(defaults) == len(names), line
+            out.update(zip(names, defaults))
+    return out
+
+
+def test_readme_switch_table_matches_what_the_library_and_the_engine_read():
+    """The switch names and defaults are written out by hand in README: every library switch has a row with the default the source
+    falls back to, and every name of the table is read by the library, by the engine's SWITCHES / GATES, or is one of the four
+    variables other modules read."""
+    lib = _library_switch_defaults()
+    assert set(lib) == LIBRARY_SWITCHES
+    readme = _readme_switch_rows()
+    for name, default in lib.items():
+        assert name in readme, f"{name} has no README row"
+        assert default == (0 if readme[name] == "auto" else int(readme[name])), name
+    engine_env = {env for _, env, *_ in E.SWITCHES + E.GATES if env}
+    assert engine_env <= set(readme), sorted(engine_env - set(readme))
+    others = {"P2P_FID_WEIGHTS", "P2P_LIB", "P2P_REHEARSE", "P2P_DP_BACKEND"}
+    for name in readme:
+        assert name in lib or name in engine_env or name in others, f"README names {name}, which nothing reads"
