@@ -10,7 +10,9 @@ proves from that, before anything touches a GPU, that a setting moves its cases 
 launchers is reached by some case.  `gpu` runs the cases: each direct case through the checker of its entry point in
 tests/test_step_launches_gpu.py (seeded operands on test-owned buffers laid out like the described views, NaN in every output
 element before the launch, a sentinel in the halo ring / the other channels of the pixels / behind the buffer that must survive,
-float64 reference, fused statistics against the f64 moments, a second launch bit-identical) plus a SHA-256 of the output bytes;
+float64 reference, fused statistics against the f64 moments, a second launch bit-identical) plus a SHA-256 of the output bytes,
+and -- the convolutions and weight gradients -- a second time with that checker's operands="lattice" (tests/lattice.py: the
+result is exact, every image is compared, the row's "exact" families count the elements that differ from the reference);
 the step case through that file's _check_step on an engine with the setting's attribute overrides.
 tests/test_switch_routes_gpu.py starts one child per setting.
 """
@@ -564,11 +566,11 @@ def _seed(cid, k):
     return int.from_bytes(hashlib.sha256(f"{cid}#{k}".encode()).digest()[:4], "little")
 
 
-def run_launch(T, name, dec, seed):
+def run_launch(T, name, dec, seed, **kw):
     """test_step_launches_gpu._reissue_one, plus the SHA-256 of every output buffer's bytes after the first launch"""
     import numpy as np
     import torch
-    launch = T.CHECKERS[name](name, dec, np.random.default_rng(seed))
+    launch = T.CHECKERS[name](name, dec, np.random.default_rng(seed), **kw)
     launch.go()
     torch.cuda.synchronize()
     for o in launch.outs:
@@ -630,7 +632,7 @@ def run_gpu(setting):
             uniq, _ = T.harvest(SL.step_desc(st[0], st[3], st[1]), st[2], {})
             doc["probes"][repr(tuple(st))] = {"signatures": sorted(repr(k) for k in uniq), "hash": step_result_hash(T, st, {})}
     for cid, case in cases_of(setting):
-        row = doc["cases"][cid] = {"routes": [], "errors": {}, "sha256": []}
+        row = doc["cases"][cid] = {"routes": [], "errors": {}, "exact": {}, "sha256": []}
         for k, (name, dec) in enumerate(resolve(case)):
             row["routes"] += [[l, c] for l, c in routes(name, dec)]
             dtype = _dtype_of(name, dec)
@@ -646,6 +648,25 @@ def run_gpu(setting):
                 row["errors"][f"{name[4:]} {fam}"] = [err, T._tol(fam, dtype)]
                 if not err < T._tol(fam, dtype):
                     doc["failures"].append(f"{cid}: {name}: {fam} error {err:.3g} >= {T._tol(fam, dtype):.3g}")
+            torch.cuda.empty_cache()
+            if T.CHECKERS[name] not in T.LATTICE_CHECKERS:
+                continue
+            # the same launch on integer-lattice operands (tests/lattice.py): the same route, every image, no tolerance.  Two
+            # routes of one case are then equal to each other because both equal the reference.
+            try:
+                errs, _ = run_launch(T, name, dec, _seed(cid + " lattice", k), operands="lattice")
+            except (AssertionError, L.P2PError) as e:
+                if "illegal" in str(e):
+                    raise
+                doc["failures"].append(f"{cid}: {name} (lattice): {e}")
+                continue
+            for fam, err in errs.items():
+                if fam.startswith("exact ") or fam == "insensitive share":
+                    row["exact"][f"{name[4:]} {fam}"] = err
+                else:           # (statistics and the normalised output keep their tolerances in this mode)
+                    row["errors"][f"{name[4:]} {fam} (lattice)"] = [err, T._tol(fam, dtype)]
+                if not err < T._tol(fam, dtype):
+                    doc["failures"].append(f"{cid}: {name} (lattice): {fam} {err:.3g} >= {T._tol(fam, dtype):.3g}")
             torch.cuda.empty_cache()
     if step is not None:
         model, S, dtype_name, B = step

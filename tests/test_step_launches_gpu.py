@@ -18,6 +18,17 @@ task tables are copied from the engine while it is alive and re-issued as fresh 
 benchmarked step issues are re-issued with hand-written arguments (test_entry_points_no_benchmarked_step_issues), and
 test_one_keras_update_per_parameter_per_step checks that a replayed step moves every parameter by exactly one Adam step.
 
+Lattice mode.  The checkers of the contractions (LATTICE_CHECKERS: convolutions, weight gradients, the indexed head's data
+gradient, column sums) take operands="lattice": operands from tests/lattice.py (small integers times a power of two, small
+integer biases, +-64 lattice steps in the channels around an input view), on which f32 accumulation is exact in any order.  View
+geometry, NaN before the launch, the sentinel around the view and the bit-identical second launch stay; ALL images are compared,
+and the compared quantity is the number of elements that differ from tests/lattice.expected -- families "exact out" / "exact dW" /
+"exact slabs" (the slab sum, and every slab element on the lattice) / "exact colsum", which pass only at 0; a mismatch message
+lists the first ten positions with got - want in lattice steps.  bf16 outputs add "insensitive share", the share of reference
+sums outside +-256 (bound 0.01: a condition on the inputs).  "stats", "stats f64" and "norm out" keep their tolerances.  The
+recorded steps of this file stay Gaussian; the lattice pass runs in tests/test_lattice_gpu.py and in the children of
+tests/test_switch_routes_gpu.py.
+
 Off-benchmark batches (test_every_launch_of_off_benchmark_steps_against_f64).  batch() has no drop_remainder and parallel.py
 puts a remainder on the earlier ranks, so a step can have any batch, and the batch picks the kernel.  What the ENGINE and the
 library's host queries pick (entry point, split-K, msplit, nsplit, statistics slots, block-resident / fused / strip / few-channel
@@ -98,6 +109,7 @@ from palette_and_histo_gan_amd import _lib as L
 from palette_and_histo_gan_amd import dataset_utils as DU
 from palette_and_histo_gan_amd import engine as E
 from tests import gpu_util as U
+from tests import lattice as LT
 from tests import step_launches as SL
 
 pytestmark = pytest.mark.gpu
@@ -343,10 +355,11 @@ def _check_grid(desc, h, w):
         assert desc["pix"] == halo * desc["row_stride"] + halo, f"view {desc} is not at the first interior pixel of a {h}x{w} image"
 
 
-def in_view(desc, x, dtype, fill_rng):
+def in_view(desc, x, dtype, fill_rng, other=None):
     """input view with the recorded geometry holding x [n,h,w,c] at the recorded channel offset.  The other channels of the pixels
-    hold random values (a kernel must not use them), the halo ring and the tail are zero (the gathering kernels read the halo as
-    the convolution's zero padding, include/p2pgan.h Conventions).  Returns (keep-alive tensor, p2p_tensor)."""
+    hold random values (a kernel must not use them; other(shape): the values to put there instead, tests/lattice.other_channels),
+    the halo ring and the tail are zero (the gathering kernels read the halo as the convolution's zero padding, include/p2pgan.h
+    Conventions).  Returns (keep-alive tensor, p2p_tensor)."""
     n, h, w, c = x.shape
     ld, coff, rs, ist = desc["ld"], desc["coff"], desc["row_stride"], desc["img_stride"]
     halo = (rs - w) // 2
@@ -360,8 +373,8 @@ def in_view(desc, x, dtype, fill_rng):
     base = flat_all.data_ptr()
     s = _shift(base, off0, esz, desc["align"])
     t = flat_all[s:s + numel].view(n, hp, wp, ld)
-    other = torch.as_tensor(U.q(fill_rng.normal(size=(n, h, w, ld)), dtype)).to(U.DEV)
-    t[:, halo:halo + h, halo:halo + w, :] = other.to(t.dtype)
+    fill = U.q(fill_rng.normal(size=(n, h, w, ld)), dtype) if other is None else other((n, h, w, ld))
+    t[:, halo:halo + h, halo:halo + w, :] = torch.as_tensor(fill).to(U.DEV).to(t.dtype)
     t[:, halo:halo + h, halo:halo + w, coff:coff + c] = torch.as_tensor(x).to(U.DEV).to(t.dtype)
     return flat_all, L.Tensor(base + (s + off0) * esz, ist, rs, ld)
 
@@ -410,9 +423,36 @@ class Launch:
         self.outs, self.go, self.evaluate = outs, go, evaluate
 
 
-def _conv_family(name, a, rng):
+def _lattice_mode(operands):
+    assert operands in ("gaussian", "lattice"), operands
+    return operands == "lattice"
+
+
+def _other(lat, rng, step):
+    """what in_view puts into the channels around the view: Gaussian values, or +-64 steps of the tensor in lattice mode"""
+    return (lambda shape: LT.other_channels(rng, shape, step)) if lat else None
+
+
+def _exact_family(errs, msgs, family, got, want, step, names):
+    """lattice mode: the number of elements that are not the expected value as a family that passes only at 0, and the first ten
+    positions with their deltas for the assertion message"""
+    errs[family] = float(len(LT.mismatches(got, want)))
+    if errs[family]:
+        msgs.append(f"{family}: " + LT.describe_mismatches(got, want, step, names))
+
+
+def _sensitive(errs, dtype, sum_int):
+    """lattice mode, bf16 outputs: the share of reference sums outside +-256 (where bf16 no longer tells every integer apart) as
+    a family bounded by 0.01.  A condition on the inputs, computed from the reference alone"""
+    if dtype == L.BF16:
+        errs["insensitive share"] = 1.0 - LT.sensitive_share(sum_int)
+
+
+def _conv_family(name, a, rng, operands="gaussian"):
     """p2p_igemm, p2p_conv_strip, p2p_igemm_norm_act (stride 2, full channel counts) and the edge forms p2p_igemm_edge,
-    p2p_conv_fewin, p2p_conv_fewout, p2p_conv_fewin_actbwd (cin_pad contracted channels, ncols outputs, stride 1 or 2)"""
+    p2p_conv_fewin, p2p_conv_fewout, p2p_conv_fewin_actbwd (cin_pad contracted channels, ncols outputs, stride 1 or 2).
+    operands="lattice": integer-lattice operands (tests/lattice.py), every image compared, the result exact"""
+    lat = _lattice_mode(operands)
     edge = name in ("p2p_igemm_edge", "p2p_conv_fewin", "p2p_conv_fewout", "p2p_conv_fewin_actbwd")
     if edge:
         op, stride, dtype, N, LH, LW, cin_pad, ncols, w_rows = a[:9]
@@ -429,9 +469,20 @@ def _conv_family(name, a, rng):
         in_shape = (2 * LH, 2 * LW, cg) if op == L.OP_G else (LH, LW, cd)
         out_shape = (LH, LW, cd) if op == L.OP_G else (2 * LH, 2 * LW, cg)
     tdt, esz = U.tdt(dtype), _esz(dtype)
-    x = U.q(rng.normal(size=(N,) + in_shape), dtype)
-    w = U.q(rng.normal(scale=1.0 / np.sqrt(16 * in_shape[2]), size=(4, 4, cg, cd)), dtype)
-    keep_in, in_v = in_view(in_d, x, dtype, rng)
+    sk = a[7 + 3] if name == "p2p_igemm" else 1
+    step = sx = 1.0
+    if lat:
+        # contraction length: 16 taps of the input channels (op G), 4 (stride 2) or 16 (stride 1) of them per output pixel (op P);
+        # split-K slabs are f32 whatever the dtype
+        K = (16 if op == L.OP_G or stride == 1 else 4) * in_shape[2]
+        out_bf16 = dtype == L.BF16 and sk == 1
+        x, sx = LT.operands(rng, (N,) + in_shape, "x", K, dtype, out_bf16)
+        w, sw = LT.operands(rng, (4, 4, cg, cd), "w", K, dtype, out_bf16)
+        step = sx * sw
+    else:
+        x = U.q(rng.normal(size=(N,) + in_shape), dtype)
+        w = U.q(rng.normal(scale=1.0 / np.sqrt(16 * in_shape[2]), size=(4, 4, cg, cd)), dtype)
+    keep_in, in_v = in_view(in_d, x, dtype, rng, _other(lat, rng, sx))
     if edge:
         if op == L.OP_G:
             wbuf = _prep(dtype, w, cg, cd, wt_shape=(w_rows, cin_pad))
@@ -442,7 +493,6 @@ def _conv_family(name, a, rng):
     nout = out_shape[2]
     res_h, res_w = out_shape[0], out_shape[1]
     outs, extra = [], {}
-    sk = a[7 + 3] if name == "p2p_igemm" else 1
     slabs = None
     out = OutBuf(out_d, N, res_h, res_w, nout, tdt, esz)      # (not written with split-K slabs)
     if name == "p2p_igemm" and sk > 1:
@@ -462,11 +512,11 @@ def _conv_family(name, a, rng):
         extra["slots"] = slots
     bias = gate = gamma = beta = None
     if name in ("p2p_igemm_edge", "p2p_conv_fewin", "p2p_conv_fewout") and a[12] is not None:
-        bias = rng.normal(size=ncols).astype(np.float32)
+        bias = LT.small_ints(rng, ncols, step) if lat else rng.normal(size=ncols).astype(np.float32)
     bias_d = U.dev(bias) if bias is not None else None
     if name == "p2p_conv_fewin_actbwd":
-        gate = U.q(rng.normal(size=(N, res_h, res_w, nout)), dtype)
-        keep_gate, gate_v = in_view(a[12][1], gate, dtype, rng)
+        gate = LT.operands(rng, (N, res_h, res_w, nout), "x", 1, dtype, True)[0] if lat else U.q(rng.normal(size=(N, res_h, res_w, nout)), dtype)
+        keep_gate, gate_v = in_view(a[12][1], gate, dtype, rng, _other(lat, rng, 1.0))
     if name == "p2p_igemm_norm_act":
         gamma = (1 + 0.2 * rng.normal(size=nout)).astype(np.float32)
         beta = (0.2 * rng.normal(size=nout)).astype(np.float32)
@@ -493,11 +543,21 @@ def _conv_family(name, a, rng):
                    U.ptr(bias_d) if bias_d is not None else None, a[13], a[14], st)
 
     def evaluate():
-        errs = {}
-        imgs = SL.image_set(N, seed=N * 7 + LH)
+        errs, msgs = {}, []
+        imgs = list(range(N)) if lat else SL.image_set(N, seed=N * 7 + LH)
         conv = (SL.conv_g(x[imgs], w, stride) if op == L.OP_G else SL.conv_p(x[imgs], w, stride))
+        where = ("image", "y", "x", "channel")
         if slabs is not None:
-            got = slabs.values().reshape(sk, N, res_h, res_w, nout).sum(0)[imgs]
+            sl = slabs.values().reshape(sk, N, res_h, res_w, nout)
+            got = sl.sum(0)[imgs]
+            if lat:     # the slab SUM is the reference and every slab element is on the lattice; which taps a slab holds is the kernel's business
+                _exact_family(errs, msgs, "exact slabs", got, LT.expected(conv, L.F32), step, where)
+                off = int((np.rint(sl / step) != sl / step).sum())
+                if off:
+                    errs["exact slabs"] += off
+                    msgs.append(f"exact slabs: {off} slab elements are no integer multiple of the lattice step")
+                assert not msgs, "; ".join(msgs)
+                return errs
             errs["f32 slabs"] = SL.per_image_err(got, conv)
             return errs
         full = out.region()
@@ -509,7 +569,17 @@ def _conv_family(name, a, rng):
         else:
             ref = conv + (bias if bias is not None else 0.0)
             ref = SL.act(ref, a[13], a[14]) if edge else ref
-        errs["out " + ("bf16" if dtype == L.BF16 else "f32")] = SL.per_image_err(got, ref)
+        if lat:
+            if name == "p2p_conv_fewin_actbwd":
+                want = LT.expected(conv, dtype, alpha=a[13], gate=gate)
+            elif edge:
+                want = LT.expected(conv, dtype, bias=bias, act=a[13], alpha=a[14])
+            else:
+                want = LT.expected(conv, dtype)         # (p2p_igemm_norm_act: the raw convolution output)
+            _exact_family(errs, msgs, "exact out", got, want, step, where)
+            _sensitive(errs, dtype, LT.to_int(conv, step) + (LT.to_int(bias, step) if bias is not None else 0))
+        else:
+            errs["out " + ("bf16" if dtype == L.BF16 else "f32")] = SL.per_image_err(got, ref)
         if spart is not None:
             mean, var = SL.pooled_moments(spart.values().reshape(N, extra["slots"], nout, 2), res_h * res_w / extra["slots"])
             errs["stats"] = SL.moment_err(mean, var, full)                       # every image: the stored output's moments
@@ -522,6 +592,7 @@ def _conv_family(name, a, rng):
             want = SL.norm_act(got, gamma, beta, a[12], a[13], a[14])
             pre = SL.norm_act(got, gamma, beta, a[12], 0, 0.0)
             errs["norm out"] = SL.per_image_channel_err(y.region()[imgs], want, np.maximum(np.abs(want), np.abs(pre)))
+        assert not msgs, "; ".join(msgs)
         return errs
 
     keep = (keep_in, wbuf, bias_d) + ((keep_gate,) if gate is not None else ()) + ((g_d, b_d) if gamma is not None else ())
@@ -530,8 +601,9 @@ def _conv_family(name, a, rng):
     return launch
 
 
-def _wgrad_family(name, a, rng):
-    """p2p_wgemm (stride 2), p2p_wgemm_edge, p2p_wgrad_small: dW over the whole batch"""
+def _wgrad_family(name, a, rng, operands="gaussian"):
+    """p2p_wgemm (stride 2), p2p_wgemm_edge, p2p_wgrad_small: dW over the whole batch.  operands="lattice": exact"""
+    lat = _lattice_mode(operands)
     if name == "p2p_wgemm":
         dtype, N, LH, LW, cg, cd = a[:6]
         stride, hi_d, lo_d, ms = 2, a[6][1], a[7][1], a[9]
@@ -539,10 +611,15 @@ def _wgrad_family(name, a, rng):
         dtype, stride, N, LH, LW, cg, cd = a[:7]
         hi_d, lo_d = a[7][1], a[8][1]
         ms = a[10] if name == "p2p_wgemm_edge" else None
-    hi = U.q(rng.normal(size=(N, stride * LH, stride * LW, cg)), dtype)
-    lo = U.q(rng.normal(size=(N, LH, LW, cd)), dtype)
-    keep_hi, hv = in_view(hi_d, hi, dtype, rng)
-    keep_lo, lv = in_view(lo_d, lo, dtype, rng)
+    s_hi = s_lo = 1.0
+    if lat:             # dW is f32 in both dtypes: the widest alphabet, K = N * LH * LW products of two activations
+        hi, s_hi = LT.operands(rng, (N, stride * LH, stride * LW, cg), "x", N * LH * LW, dtype, False)
+        lo, s_lo = LT.operands(rng, (N, LH, LW, cd), "x", N * LH * LW, dtype, False)
+    else:
+        hi = U.q(rng.normal(size=(N, stride * LH, stride * LW, cg)), dtype)
+        lo = U.q(rng.normal(size=(N, LH, LW, cd)), dtype)
+    keep_hi, hv = in_view(hi_d, hi, dtype, rng, _other(lat, rng, s_hi))
+    keep_lo, lv = in_view(lo_d, lo, dtype, rng, _other(lat, rng, s_lo))
     dw = FlatOut(16 * cg * cd, a[8 if name == "p2p_wgemm" else 9][1])
     if name == "p2p_wgrad_small":
         nb = L.lib().p2p_wgrad_small_blocks(dtype, stride, N, LH, LW, cg, cd, hv.ld, lv.ld)
@@ -563,6 +640,12 @@ def _wgrad_family(name, a, rng):
 
     def evaluate():
         ref = SL.conv_w(hi, lo, stride)
+        if lat:
+            errs, msgs = {}, []
+            _exact_family(errs, msgs, "exact dW", dw.values().reshape(4, 4, cg, cd), LT.expected(ref, L.F32), s_hi * s_lo,
+                          ("kh", "kw", "g", "d"))
+            assert not msgs, "; ".join(msgs)
+            return errs
         k = N * LH * LW
         # K = N*LH*LW products of activation-dtype values (exact in f32), summed in f32 in a fixed blocked order.  The rounding
         # error of a sum of K random-sign terms grows like sqrt(K) * 2^-24 relative to the result; 4 * sqrt(K) * 2^-24 is 2e-5
@@ -876,13 +959,22 @@ def _hist_bwd3(name, a, rng):
     return launch
 
 
-def _head_dgrad(name, a, rng):
-    """p2p_head_dgrad: op P, stride 1, of the indexed head into the first `cout` channels of the output view"""
+def _head_dgrad(name, a, rng, operands="gaussian"):
+    """p2p_head_dgrad: op P, stride 1, of the indexed head into the first `cout` channels of the output view.
+    operands="lattice": every image, exact"""
+    lat = _lattice_mode(operands)
     dtype, N, H, W, ncls, cout = a[:6]
     w_rows = a[8]
-    dz = U.q(rng.normal(size=(N, H, W, ncls)), dtype)
-    keep, dzv = in_view(a[6][1], dz, dtype, rng)
-    w = U.q(rng.normal(scale=1.0 / np.sqrt(16 * ncls), size=(4, 4, cout, ncls)), dtype)
+    step = sx = 1.0
+    if lat:
+        dz, sx = LT.operands(rng, (N, H, W, ncls), "x", 16 * ncls, dtype, dtype == L.BF16)
+        w, sw = LT.operands(rng, (4, 4, cout, ncls), "w", 16 * ncls, dtype, dtype == L.BF16)
+        step = sx * sw
+        keep, dzv = in_view(a[6][1], dz, dtype, rng, _other(lat, rng, sx))
+    else:
+        dz = U.q(rng.normal(size=(N, H, W, ncls)), dtype)
+        keep, dzv = in_view(a[6][1], dz, dtype, rng)
+        w = U.q(rng.normal(scale=1.0 / np.sqrt(16 * ncls), size=(4, 4, cout, ncls)), dtype)
     wn = _prep(dtype, w, cout, ncls, wn_shape=(w_rows, ncls))
     out = OutBuf(a[9][1], N, H, W, cout, U.tdt(dtype), _esz(dtype))
 
@@ -890,6 +982,13 @@ def _head_dgrad(name, a, rng):
         L.call(name, dtype, N, H, W, ncls, cout, C.byref(dzv), U.ptr(wn), w_rows, C.byref(out.view), U.stream())
 
     def evaluate():
+        if lat:
+            errs, msgs = {}, []
+            conv = SL.conv_p(dz, w, 1)
+            _exact_family(errs, msgs, "exact out", out.region(), LT.expected(conv, dtype), step, ("image", "y", "x", "channel"))
+            _sensitive(errs, dtype, LT.to_int(conv, step))
+            assert not msgs, "; ".join(msgs)
+            return errs
         imgs = SL.image_set(N, seed=N + 11)
         return {"out bf16": SL.per_image_err(out.region()[imgs], SL.conv_p(dz[imgs], w, 1))}
 
@@ -1277,10 +1376,15 @@ def _hist_normalize(name, a, rng):
 
 
 # ---- reductions
-def _colsum(name, a, rng):
-    """p2p_colsum: out[c] = scale * sum_r part[r][c]"""
+def _colsum(name, a, rng, operands="gaussian"):
+    """p2p_colsum: out[c] = scale * sum_r part[r][c].  operands="lattice": exact (one f32 multiply by the scale, which rounds once
+    whether it is applied to the sum or -- a power of two -- to the terms)"""
+    lat = _lattice_mode(operands)
     rows, cols, scale = a[1], a[2], a[3]
-    part = rng.normal(0.3, 1.0, size=(rows, cols)).astype(np.float32)
+    if lat:
+        part, step = LT.operands(rng, (rows, cols), "x", rows, L.F32, False)
+    else:
+        part = rng.normal(0.3, 1.0, size=(rows, cols)).astype(np.float32)
     pd = U.dev(part.reshape(-1))
     out = FlatOut(cols, a[4][1])
 
@@ -1288,6 +1392,12 @@ def _colsum(name, a, rng):
         L.call(name, U.ptr(pd), rows, cols, scale, out.ptr(), U.stream())
 
     def evaluate():
+        if lat:
+            errs, msgs = {}, []
+            want = np.float32(scale) * LT.expected(part.astype(np.float64).sum(axis=0), L.F32)
+            _exact_family(errs, msgs, "exact colsum", out.values(), want, step * scale, ("column",))
+            assert not msgs, "; ".join(msgs)
+            return errs
         return {"colsum f32": _rel(out.values(), scale * part.astype(np.float64).sum(axis=0)) / _long_k(rows)}
 
     launch = Launch([out], go, evaluate)
@@ -1295,11 +1405,16 @@ def _colsum(name, a, rng):
     return launch
 
 
-def _view_colsum(name, a, rng):
-    """p2p_view_colsum: column sums over every pixel of a view (bias gradients), with its workspace"""
+def _view_colsum(name, a, rng, operands="gaussian"):
+    """p2p_view_colsum: column sums over every pixel of a view (bias gradients), with its workspace.  operands="lattice": exact"""
+    lat = _lattice_mode(operands)
     dtype, N, H, W, Cc = a[:5]
-    x = U.q(rng.normal(0.3, 1.0, size=(N, H, W, Cc)), dtype)
-    keep, vv = in_view(a[5][1], x, dtype, rng)
+    step = 1.0
+    if lat:
+        x, step = LT.operands(rng, (N, H, W, Cc), "x", N * H * W, dtype, False)
+    else:
+        x = U.q(rng.normal(0.3, 1.0, size=(N, H, W, Cc)), dtype)
+    keep, vv = in_view(a[5][1], x, dtype, rng, _other(lat, rng, step))
     out = FlatOut(Cc, a[6][1])
     need = L.lib().p2p_view_colsum_workspace_bytes(dtype, N, H, W, Cc, C.byref(vv)) // 4
     ws = torch.full((max(need, 16),), float("nan"), dtype=torch.float32, device=U.DEV)
@@ -1308,6 +1423,12 @@ def _view_colsum(name, a, rng):
         L.call(name, dtype, N, H, W, Cc, C.byref(vv), out.ptr(), U.ptr(ws), U.stream())
 
     def evaluate():
+        if lat:
+            errs, msgs = {}, []
+            _exact_family(errs, msgs, "exact colsum", out.values(), LT.expected(x.astype(np.float64).sum(axis=(0, 1, 2)), L.F32), step,
+                          ("column",))
+            assert not msgs, "; ".join(msgs)
+            return errs
         return {"colsum f32": _rel(out.values(), x.astype(np.float64).sum(axis=(0, 1, 2))) / _long_k(N * H * W)}
 
     launch = Launch([out], go, evaluate)
@@ -1315,14 +1436,18 @@ def _view_colsum(name, a, rng):
     return launch
 
 
-def _colsum_batched(name, a, rng):
+def _colsum_batched(name, a, rng, operands="gaussian"):
     """p2p_colsum_batched: task {part_off, rows, cols, out_off} sums a [rows][cols] block into out + out_off; the rest of the
-    output buffer (the recorded one is the generator's flat gradient buffer) keeps its values"""
+    output buffer (the recorded one is the generator's flat gradient buffer) keeps its values.  operands="lattice": exact"""
+    lat = _lattice_mode(operands)
     tasks = [tuple(t) for t in a[1][1]]
     ntasks, maxc = a[2], a[3]
     numel = a[4][2] - a[4][3]
     assert len(tasks) == ntasks and maxc == max(t[2] for t in tasks), (ntasks, maxc, tasks)
-    part = rng.normal(0.3, 1.0, size=max(po + r * c for po, r, c, _ in tasks)).astype(np.float32)
+    if lat:
+        part, step = LT.operands(rng, (max(po + r * c for po, r, c, _ in tasks),), "x", max(t[1] for t in tasks), L.F32, False)
+    else:
+        part = rng.normal(0.3, 1.0, size=max(po + r * c for po, r, c, _ in tasks)).astype(np.float32)
     pd = U.dev(part)
     written = torch.zeros(numel, dtype=torch.bool)
     for _, _, c, oo in tasks:
@@ -1336,9 +1461,17 @@ def _colsum_batched(name, a, rng):
     def evaluate():
         got = out.body().double().cpu().numpy()
         e = 0.0
-        for po, r, c, oo in tasks:
+        errs, msgs = {"exact colsum": 0.0}, []
+        for k, (po, r, c, oo) in enumerate(tasks):
             want = part[po:po + r * c].astype(np.float64).reshape(r, c).sum(axis=0)
+            if lat:
+                one = {}
+                _exact_family(one, msgs, f"exact colsum (task {k})", got[oo:oo + c], LT.expected(want, L.F32), step, ("column",))
+                errs["exact colsum"] += sum(one.values())
             e = max(e, _rel(got[oo:oo + c], want) / _long_k(r))
+        if lat:
+            assert not msgs, "; ".join(msgs)
+            return errs
         return {"colsum f32": e}
 
     launch = Launch([out], go, evaluate)
@@ -1754,7 +1887,15 @@ CHECKERS.update({"p2p_bce_logits": _bce, "p2p_bce_logits_pad8": _bce, "p2p_tanh_
                  "p2p_counter_add": _counter_add})
 
 
+# the checkers with an operands="lattice" mode (tests/lattice.py): the contractions, whose f32 accumulation is exact on such operands
+LATTICE_CHECKERS = (_conv_family, _wgrad_family, _head_dgrad, _view_colsum, _colsum, _colsum_batched)
+
+
 def _tol(family, dtype):
+    if family.startswith("exact "):
+        return 1.0              # lattice mode: a count of elements that are not the expected value; passes only at 0
+    if family == "insensitive share":
+        return 0.01 + 1e-12     # lattice mode, bf16: at least 0.99 of the reference sums lie within +-256
     if family.startswith("out") or family == "stats f64":
         return OUT_TOL[dtype]
     if family.startswith("d(raw)"):

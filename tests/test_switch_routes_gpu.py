@@ -15,12 +15,16 @@ attribute overrides, and reports routes, errors and output hashes as JSON.  Here
     P2P_WS_SWIZZLE=0           only the place of a pixel's 64-byte chunks in the LDS strip
   and bit-identical STEP results (losses of two steps, every parameter after them) for fuse_act_bwd=0 and split_prep=0, which move
   work between launches (switch_routes.STEP_BIT_IDENTICAL).
-  Everything else changes the order of a sum and is held to the tolerance only: another K-loop / K-group split (P2P_IGEMM_PIPE,
-  P2P_IGEMM_BIG: the 256-row tile, the second K group), one or two taps per wave and the packed-tap tiles (P2P_WS_W16, P2P_WS_PACK:
-  other MFMA accumulation chains), wgemm_kernel's K blocking against the pipelined kernel's (P2P_WGEMM_PIPE), two-pass against
-  register-resident statistics (P2P_NORM_*_REG), the im2col kernels against the block-resident one (P2P_BRIG), the unfused
-  statistics (P2P_BRIG_FUSE_NORM), other K splits (splitk_target, wgemm_pipe's msplit) and other kernels altogether (use_conv_*,
-  use_head_fused).
+  Everything else changes the order of a sum: another K-loop / K-group split (P2P_IGEMM_PIPE, P2P_IGEMM_BIG: the 256-row tile,
+  the second K group), one or two taps per wave and the packed-tap tiles (P2P_WS_W16, P2P_WS_PACK: other MFMA accumulation
+  chains), wgemm_kernel's K blocking against the pipelined kernel's (P2P_WGEMM_PIPE), two-pass against register-resident
+  statistics (P2P_NORM_*_REG), the im2col kernels against the block-resident one (P2P_BRIG), the unfused statistics
+  (P2P_BRIG_FUSE_NORM), other K splits (splitk_target, wgemm_pipe's msplit) and other kernels altogether (use_conv_*,
+  use_head_fused).  On Gaussian operands such a route is held to the tolerance only.  Every direct convolution and weight-gradient
+  case therefore runs a second time in the same child on integer-lattice operands (tests/lattice.py; the row's "exact" families),
+  where the f32 accumulation is exact in any order: the stored result must be the integer reference bit for bit, on every image
+  -- 0 mismatches, no tolerance -- so two routes of one case are equal to each other because both equal the reference.  (The
+  normalisation cases and the step cases stay Gaussian: their sums are not contractions of products.)
 - for the two engine switches the meta device cannot see (switch_routes.CENSUS_BLIND) the recorded step's launch signatures differ
   from the default engine's.
 
@@ -30,10 +34,16 @@ this module then fails at once WITHOUT starting another child, and nothing is re
 Timeout: on the first run on an MI355X the slowest test took 13.7 s (use_conv_strip=False: its GPU child with the step case, about
 10 s, of which 3-4 s are the start-up, plus the query child); the `default` child with its 113 direct cases and two step probes took
 under 11.5 s.  3 x the slowest child, rounded up: 45 s.
+With the lattice pass (every convolution / weight-gradient case a second time, all images against the integer reference), measured
+per GPU child on an MI355X (each test prints its child's time): default 8.2 s; the slowest are P2P_IGEMM_PIPE=2 and P2P_IGEMM_BIG=0
+at 10.6 s each (the 49- and 256-image cases plus a step case), then wgemm_pipe=False 7.8 s, P2P_BRIG=0 7.5 s and P2P_BRIG_STAGGER=0
+7.0 s; every other child took 2.4 - 6.8 s, and the slowest test (default, with its query child) 13.0 s.  No child exceeds 15 s: the
+timeout stays at 45 s.
 """
 import json
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -44,12 +54,14 @@ pytestmark = pytest.mark.gpu
 CHILD_TIMEOUT = 45           # seconds: 3 x the slowest child (module docstring)
 _FATAL = []                  # set by the first child that faulted, hung or aborted: no further child is started
 _DOCS = {}
+_SECONDS = {}                # (setting, mode) -> wall time of the child, printed with the setting's table
 
 
 def _run(name, mode):
     if _FATAL:
         pytest.fail(f"not started: an earlier child was fatal ({_FATAL[0]})")
     cmd = [sys.executable, "-m", "tests.switch_routes", "--setting", name, "--mode", mode]
+    t0 = time.monotonic()
     try:
         r = subprocess.run(cmd, cwd=R.ROOT, env=R.child_env(name), capture_output=True, text=True, timeout=CHILD_TIMEOUT)
     except subprocess.TimeoutExpired:
@@ -60,6 +72,7 @@ def _run(name, mode):
         _FATAL.append(f"{name} ({mode}): return code {r.returncode}")
         pytest.fail(_FATAL[0] + "\n" + text[-3000:])
     assert r.returncode == 0, f"{name} ({mode}): return code {r.returncode}\n{text[-3000:]}"
+    _SECONDS[(name, mode)] = time.monotonic() - t0
     return json.loads(r.stdout), r.stderr
 
 
@@ -78,13 +91,19 @@ def _modelled(keys):
 def test_switch_setting_against_f64(name):
     env, attrs, base, groups, step = R.SETTINGS[name]
     doc, log = _doc(name)
-    print(f"\n[{name}] " + " ".join(f"{k}={v}" for k, v in {**env, **attrs}.items()))
+    print(f"\n[{name}] " + " ".join(f"{k}={v}" for k, v in {**env, **attrs}.items()) + f" (GPU child: {_SECONDS[(name, 'gpu')]:.1f} s)")
     for cid, row in doc["cases"].items():
         errs = ", ".join(f"{f} {e:.2e} ({t:.0e})" for f, (e, t) in sorted(row["errors"].items()))
-        print(f"  {cid:48s} {' + '.join(R.describe(l, c) for l, c in row['routes']):60s} {errs}")
+        exact = ", ".join(f"{f} {e:.4f}" if f.endswith("share") else f"{f} {int(e)}" for f, e in sorted(row.get("exact", {}).items()))
+        print(f"  {cid:48s} {' + '.join(R.describe(l, c) for l, c in row['routes']):60s} {errs}" + (f" | lattice: {exact}" if exact else ""))
     if step is not None:
         print(log[log.find(f"[{name}"):] if f"[{name}" in log else log[-2000:])       # the table _check_step printed in the child
     assert not doc["failures"], "\n".join(doc["failures"])
+    # the lattice pass: every convolution / weight-gradient case reports its exact families, all at 0 mismatches
+    for cid, row in doc["cases"].items():
+        counts = [e for f, e in row["exact"].items() if " exact " in f]
+        assert cid.startswith("norm ") or counts, f"{cid}: no lattice run"
+        assert not any(counts), f"{cid}: {row['exact']}"
     want, _ = _doc(name, "query")
     assert {c: r["routes"] for c, r in doc["cases"].items()} == {c: r["routes"] for c, r in want["cases"].items()}, \
         "a case ran on another route than the host query gives"
