@@ -5,7 +5,63 @@
 #include "p2p_common.hpp"
 #include <stdlib.h>
 
+#include <type_traits>
+
 typedef __attribute__((__vector_size__(2 * sizeof(float)))) float f32x2;
+
+// ---------------------------------------------------------------------------------------------------
+// The per-element math, one definition each: every form below (scalar, lane-group, register-resident, workgroup, 1x1) calls
+// these, so the forms cannot drift apart by an ulp (a ReLU gate that flips on such a difference is an 8 % error on that element).
+__device__ __forceinline__ float act_apply(float y, int act, float alpha) {
+    if (act == P2P_ACT_LEAKY) return y > 0.f ? y : alpha * y;
+    if (act == P2P_ACT_RELU) return y > 0.f ? y : 0.f;
+    return y;
+}
+// d(act)/d(a) at the pre-activation value a
+__device__ __forceinline__ float act_slope(float a, int act, float alpha) {
+    if (act == P2P_ACT_LEAKY) return a > 0.f ? 1.f : alpha;
+    if (act == P2P_ACT_RELU) return a > 0.f ? 1.f : 0.f;
+    return 1.f;
+}
+
+// Dropout mask of one 16-byte vector (VN = 8 or 4 channels, one byte each), kept packed; keep factor of channel k: 2 or 0.
+// The vector forms drop as y * keep.  The scalar kernels drop as mask ? 2 y : 0 and are NOT expressed through this: a dropped
+// negative y is -0 here (and alpha * -0 = -0 through LeakyReLU) but +0 there, and a non-finite y gives NaN here but 0 there.
+// Each form keeps what it has always computed.
+template <int VN> using mask_word = typename std::conditional<VN == 8, unsigned long long, unsigned>::type;
+template <int VN>
+__device__ __forceinline__ mask_word<VN> mask_vload(const unsigned char* m) { return *(const mask_word<VN>*)m; }
+template <typename M>
+__device__ __forceinline__ float mask_keep(M mk, int k) { return ((mk >> (8 * k)) & 0xff) ? 2.f : 0.f; }
+template <int VN>
+__device__ __forceinline__ void mask_vkeep(const unsigned char* m, float* keep) {
+    const mask_word<VN> mk = mask_vload<VN>(m);
+#pragma unroll
+    for (int k = 0; k < VN; ++k) keep[k] = mask_keep(mk, k);
+}
+
+__device__ __forceinline__ float norm_xhat(float x, float mu, float rs) { return (x - mu) * rs; }
+
+// Forward element of the vector forms in its two steps, normalise and dropout -> activation (kernels whose normalisation is
+// optional take the first step only when they normalise), and the whole of it.  keep: the dropout factor, 1 without dropout.
+__device__ __forceinline__ float norm_affine(float x, float mu, float rs, float ga, float be) { return norm_xhat(x, mu, rs) * ga + be; }
+__device__ __forceinline__ float drop_act(float y, bool drop, float keep, int act, float alpha) {
+    if (drop) y *= keep;
+    return act_apply(y, act, alpha);
+}
+__device__ __forceinline__ float fwd_elem(float x, float mu, float rs, float ga, float be, bool drop, float keep, int act, float alpha) {
+    return drop_act(norm_affine(x, mu, rs, ga, be), drop, keep, act, alpha);
+}
+
+// Backward element: d(yhat) of one value from xhat (the value itself without normalisation), the dropout factor keep (1 without
+// dropout) and the incoming gradient da.  yhat = the normalised value before dropout / activation.
+__device__ __forceinline__ float bwd_elem(bool norm, float xh, float ga, float be, float keep, float da, int act, float alpha) {
+    float a = norm ? xh * ga + be : xh;
+    a *= keep;
+    return da * act_slope(a, act, alpha) * keep;
+}
+// d(x) from d(yhat) = d, with m1 = mean(d) and m2 = mean(d * xhat) over the image (closed form)
+__device__ __forceinline__ float bwd_dx(float ga, float rs, float d, float m1, float xh, float m2) { return ga * rs * (d - m1 - xh * m2); }
 
 // one workgroup = one image x CB consecutive channels; threads = (pixel lane) x (channel)
 template <typename T>
@@ -71,12 +127,10 @@ __global__ void norm_act_fwd_kernel(int H, int W, int C, int CB, const void* __r
         long long e = base + (long long)p * C;
         float x = raw_load<T>(raw, raw_kind, nslabs, slab, e);
         if (raw_out) raw_out[e] = from_f32<T>(x);
-        float y = gamma ? (x - mu) * r * ga + be : x;
-        if (mask) y = mask[e] ? y * 2.f : 0.f;
-        if (act == P2P_ACT_LEAKY) y = y > 0.f ? y : alpha * y;
-        else if (act == P2P_ACT_RELU) y = y > 0.f ? y : 0.f;
+        float y = gamma ? norm_xhat(x, mu, r) * ga + be : x;
+        if (mask) y = mask[e] ? y * 2.f : 0.f;       // (the scalar dropout form: see mask_vload)
         int yy = p / W, xx = p - yy * W;
-        ((T*)out.ptr)[out.off(n, yy, xx) + c0 + c] = from_f32<T>(y);
+        ((T*)out.ptr)[out.off(n, yy, xx) + c0 + c] = from_f32<T>(act_apply(y, act, alpha));
     }
 }
 
@@ -109,15 +163,11 @@ __global__ void norm_act_bwd_kernel(int H, int W, int C, int CB, const T* __rest
     auto dyhat = [&](int p, float& xh) -> float {
         long long e = base + (long long)p * C;
         float x = to_f32(raw[e]);
-        xh = gamma ? (x - mu) * r : x;
-        float a = gamma ? xh * ga + be : x;
+        xh = gamma ? norm_xhat(x, mu, r) : x;
         float keep = 1.f;
-        if (mask) { keep = mask[e] ? 2.f : 0.f; a *= keep; }
+        if (mask) keep = mask[e] ? 2.f : 0.f;
         float da = gsrc_load<T>(g1, pix0 + p, c0 + c) + gsrc_load<T>(g2, pix0 + p, c0 + c);
-        float slope = 1.f;
-        if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
-        else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
-        return da * slope * keep;
+        return bwd_elem(gamma, xh, ga, be, keep, da, act, alpha);
     };
 
     float m1 = 0.f, m2 = 0.f;
@@ -148,7 +198,7 @@ __global__ void norm_act_bwd_kernel(int H, int W, int C, int CB, const T* __rest
     for (int p = pl; p < HW; p += PL) {
         float xh;
         float d = dyhat(p, xh);
-        float dx = gamma ? ga * r * (d - m1 - xh * m2) : d;
+        float dx = gamma ? bwd_dx(ga, r, d, m1, xh, m2) : d;
         int yy = p / W, xx = p - yy * W;
         ((T*)draw.ptr)[draw.off(n, yy, xx) + c0 + c] = from_f32<T>(dx);
     }
@@ -178,20 +228,13 @@ __device__ __forceinline__ void vstore(T* p, const float* v) {
     *(typename VecOf<T>::type*)p = r;
 }
 
-// SLABS: 1 = f32 split-K slabs summed one by one (the two-pass kernels: the unrolled form below costs them registers -- the
-// 64x64x32 backward launch of c2 went 68 -> 96 us with it), 4 = four slabs per trip, 0 = dense input only (the slab code and
-// its registers are compiled out: the host picks the instantiation by what the launch reads).
-template <typename T, int SLABS = 1>
-__device__ __forceinline__ void raw_vload(const void* raw, int raw_kind, int nslabs, long long slab, long long e, float* v) {
-    constexpr int VN = VecOf<T>::N;
-    if (SLABS == 0 || raw_kind == 1) { vload<T>((const T*)raw + e, v); return; }
-#pragma unroll
-    for (int k = 0; k < VN; ++k) v[k] = 0.f;
-    const float* p = (const float*)raw + e;
-    // four slabs per trip: their loads are issued together, the sums keep the slab order (a small batch reads 4-16 slabs per
-    // element and the one-slab loop was a chain of dependent memory latencies: c1 14 us for 32 K elements)
+// Four f32 slabs per trip, in whole 16-byte loads: v += slabs 0 ... 4 * (nslabs / 4) - 1 of the VN values at p; returns the first
+// slab not added.  The loads of a trip are issued together, the sums keep the slab order (a small batch reads 4-16 slabs per
+// element and the one-slab loop was a chain of dependent memory latencies: c1 14 us for 32 K elements)
+template <int VN>
+__device__ __forceinline__ int slabs4_add(const float* p, long long slab, int nslabs, float* v) {
     int sIdx = 0;
-    for (; SLABS == 4 && sIdx + 4 <= nslabs; sIdx += 4) {
+    for (; sIdx + 4 <= nslabs; sIdx += 4) {
         f32x4 r[4][VN / 4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -204,6 +247,20 @@ __device__ __forceinline__ void raw_vload(const void* raw, int raw_kind, int nsl
                 v[k] += r[u][k / 4][0]; v[k + 1] += r[u][k / 4][1]; v[k + 2] += r[u][k / 4][2]; v[k + 3] += r[u][k / 4][3];
             }
     }
+    return sIdx;
+}
+
+// SLABS: 1 = f32 split-K slabs summed one by one (the two-pass kernels: the unrolled form above costs them registers -- the
+// 64x64x32 backward launch of c2 went 68 -> 96 us with it), 4 = four slabs per trip, 0 = dense input only (the slab code and
+// its registers are compiled out: the host picks the instantiation by what the launch reads).
+template <typename T, int SLABS = 1>
+__device__ __forceinline__ void raw_vload(const void* raw, int raw_kind, int nslabs, long long slab, long long e, float* v) {
+    constexpr int VN = VecOf<T>::N;
+    if (SLABS == 0 || raw_kind == 1) { vload<T>((const T*)raw + e, v); return; }
+#pragma unroll
+    for (int k = 0; k < VN; ++k) v[k] = 0.f;
+    const float* p = (const float*)raw + e;
+    int sIdx = SLABS == 4 ? slabs4_add<VN>(p, slab, nslabs, v) : 0;
     for (; sIdx < nslabs; ++sIdx) {
 #pragma unroll
         for (int k = 0; k < VN; k += 4) {
@@ -229,37 +286,54 @@ __device__ __forceinline__ void gsrc_vload(const GSrc& g, long long pix, int c, 
     for (int k = 0; k < VN; ++k) v[k] = 0.f;
     const float* p = (const float*)g.ptr + e;
     int sIdx = 0;
-    if (SLABS == 4 && (g.slab & 3) == 0 && (e & 3) == 0 && ((uintptr_t)g.ptr & 15) == 0) {         // whole 16-byte loads, four slabs per trip, sums in slab order (see raw_vload)
-        for (; sIdx + 4 <= g.nslabs; sIdx += 4) {
-            f32x4 r[4][VN / 4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int k = 0; k < VN; k += 4) r[u][k / 4] = *(const f32x4*)(p + (long long)(sIdx + u) * g.slab + k);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int k = 0; k < VN; k += 4) {
-                    v[k] += r[u][k / 4][0]; v[k + 1] += r[u][k / 4][1]; v[k + 2] += r[u][k / 4][2]; v[k + 3] += r[u][k / 4][3];
-                }
-        }
-    }
+    // a gradient source carries no alignment promise: the four-slab trips only where every load is a whole 16 bytes
+    if (SLABS == 4 && (g.slab & 3) == 0 && (e & 3) == 0 && ((uintptr_t)g.ptr & 15) == 0) sIdx = slabs4_add<VN>(p, g.slab, g.nslabs, v);
     for (; sIdx < g.nslabs; ++sIdx)
 #pragma unroll
         for (int k = 0; k < VN; ++k) v[k] += p[(long long)sIdx * g.slab + k];
 }
 
-__device__ __forceinline__ void mask_vload8(const unsigned char* m, float* keep, int VN) {
-    if (VN == 8) {
-        unsigned long long r = *(const unsigned long long*)m;
+// Per-channel coefficients of a lane's VN channels c ... c + VN - 1 of image n
+template <int VN> struct Coef { float mu[VN], rs[VN], ga[VN], be[VN]; };
+
+// backward: mean and rstd as the forward pass stored them, gamma and beta
+template <int VN>
+__device__ __forceinline__ void coef_load(const float* stats, const float* gamma, const float* beta, int n, int C, int c, Coef<VN>& co) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) keep[k] = ((r >> (8 * k)) & 0xff) ? 2.f : 0.f;
-    } else {
-        unsigned r = *(const unsigned*)m;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) keep[k] = ((r >> (8 * k)) & 0xff) ? 2.f : 0.f;
+    for (int k = 0; k < VN; ++k) {
+        co.mu[k] = stats[((long long)n * C + c + k) * 2 + 0];
+        co.rs[k] = stats[((long long)n * C + c + k) * 2 + 1];
+        co.ga[k] = gamma[c + k];
+        co.be[k] = beta[c + k];
     }
 }
+
+// forward: from the image-wide sums t1 = sum(x - sh), t2 = sum((x - sh)^2) over HW pixels; `write`: this thread stores the statistics
+template <int VN>
+__device__ __forceinline__ void coef_from_sums(const float* t1, const float* t2, const float* sh, int HW, float eps, const float* gamma,
+                                               const float* beta, float* stats, bool write, int n, int C, int c, Coef<VN>& co) {
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        const float m = t1[k] / (float)HW;
+        const float var = fmaxf(t2[k] / (float)HW - m * m, 0.f);
+        co.mu[k] = sh[k] + m;
+        co.rs[k] = rsqrtf(var + eps);
+        co.ga[k] = gamma[c + k];
+        co.be[k] = beta[c + k];
+        if (write) {
+            stats[((long long)n * C + c + k) * 2 + 0] = co.mu[k];
+            stats[((long long)n * C + c + k) * 2 + 1] = co.rs[k];
+        }
+    }
+}
+
+// Workgroup decomposition of the workgroup ("vec") and register-resident forms: 256 threads = PR pixel rows x VPP lanes; a lane
+// owns the VN channels from c of the pixels pr, pr + PR, ... of its workgroup's channel group [cg0, cg0 + CG)
+template <int VN> struct WgGeom {
+    int VPP, PR, vid, pr, c;
+    __device__ __forceinline__ WgGeom(int CG, int cg0)
+        : VPP(CG / VN), PR(256 / VPP), vid(threadIdx.x % VPP), pr(threadIdx.x / VPP), c(cg0 + vid * VN) {}
+};
 
 // Column totals of two per-thread partial vectors over the PR pixel rows of a 256-thread workgroup (fixed order, so
 // deterministic).  Three short LDS stages instead of every thread re-adding all PR rows: (1) partials to red[.][pr][CG],
@@ -333,6 +407,46 @@ __device__ __forceinline__ void col_reduce2(float (*red)[2048], int CG, int PR, 
     for (int k = 0; k < VN; ++k) { t1[k] = red[0][256 + vid * VN + k]; t2[k] = red[1][256 + vid * VN + k]; }
 }
 
+// Pixel-split partials (MODE 1 / 2 of the workgroup forms below, forward and backward): launch 1 leaves the column totals t1, t2 of
+// split sp at ws[n][sp][c][2] ...
+template <int VN>
+__device__ __forceinline__ void split_store(float* ws, int n, int SP, int sp, int C, int c, const float* t1, const float* t2) {
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        ws[(((long long)n * SP + sp) * C + c + k) * 2 + 0] = t1[k];
+        ws[(((long long)n * SP + sp) * C + c + k) * 2 + 1] = t2[k];
+    }
+}
+// ... launch 2 adds the SP split partials once per workgroup (one thread per channel, fixed order i = 0 ... SP - 1) and shares
+// the totals through LDS
+template <int VN>
+__device__ __forceinline__ void split_sum(const float* ws, float (*red)[2048], int n, int SP, int C, int cg0, int CG, int vid,
+                                          float* t1, float* t2) {
+    if (threadIdx.x < CG) {
+        const int cc = cg0 + threadIdx.x;
+        float a1 = 0.f, a2 = 0.f;
+        for (int i = 0; i < SP; ++i) {
+            const f32x2 v = *(const f32x2*)(ws + (((long long)n * SP + i) * C + cc) * 2);
+            a1 += v[0]; a2 += v[1];
+        }
+        red[0][threadIdx.x] = a1;
+        red[1][threadIdx.x] = a2;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < VN; ++k) { t1[k] = red[0][vid * VN + k]; t2[k] = red[1][vid * VN + k]; }
+}
+
+// Tail of norm_act_fwd_vec: the channels that follow this layer's slice in the concat buffer (vectors t0 ... tail_vecs - 1 of them)
+// are copied by the lane that wrote the slice's last vector, so the pixel leaves the wave complete (no partially written 32-byte
+// sectors in HBM).  The vectors are moved packed, never through f32: a copy that changes no bit (a round trip through f32 would
+// quiet a signalling bf16 NaN).
+template <typename T>
+__device__ __forceinline__ void tail_copy(T* dst, const T* src, int t0, int tail_vecs) {
+    typedef typename VecOf<T>::type vec_t;
+    for (int t = t0; t < tail_vecs; ++t) *(vec_t*)(dst + t * VecOf<T>::N) = *(const vec_t*)(src + t * VecOf<T>::N);
+}
+
 // MODE 0: one launch per layer (statistics + apply, grid.z = 1 when normalising).
 // MODE 1 / 2: the pixel range of every image is split over grid.z workgroups; launch 1 writes per-split partial
 // sums to ws[N][SP][C][2], launch 2 adds them up (fixed order: deterministic) and applies.  Used when one workgroup
@@ -350,14 +464,13 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
     const int n = blockIdx.x;
     const int cg0 = blockIdx.y * CG;
     const int SP = gridDim.z, sp = blockIdx.z;
-    const int VPP = CG / VN, PR = 256 / VPP;
-    const int vid = threadIdx.x % VPP, pr = threadIdx.x / VPP;
-    const int c = cg0 + vid * VN;
+    const WgGeom<VN> wg(CG, cg0);
+    const int PR = wg.PR, vid = wg.vid, pr = wg.pr, c = wg.c;
     const int HW = H * W;
     const int chunk = (HW + SP - 1) / SP;
     const int pb = sp * chunk, pe = min(HW, pb + chunk);
     const long long base = (long long)n * HW * C + c;
-    float mu[VN], rs[VN], ga[VN], be[VN];
+    Coef<VN> co;
     if (gamma) {
         float sh[VN], t1[VN], t2[VN];
         if (MODE != 3) raw_vload<T>(raw, raw_kind, nslabs, slab, base, sh);        // image-wide shift: the first pixel's value
@@ -373,29 +486,11 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
             }
             col_reduce2<VN>(red, CG, PR, vid, pr, s1, s2, t1, t2);
             if (MODE == 1) {
-                if (pr == 0)
-#pragma unroll
-                    for (int k = 0; k < VN; ++k) {
-                        ws[(((long long)n * SP + sp) * C + c + k) * 2 + 0] = t1[k];
-                        ws[(((long long)n * SP + sp) * C + c + k) * 2 + 1] = t2[k];
-                    }
+                if (pr == 0) split_store<VN>(ws, n, SP, sp, C, c, t1, t2);
                 return;
             }
         } else if (MODE == 2) {
-            // add the SP split partials once per workgroup (one thread per channel, fixed order), share through LDS
-            if (threadIdx.x < CG) {
-                const int cc = cg0 + threadIdx.x;
-                float a1 = 0.f, a2 = 0.f;
-                for (int i = 0; i < SP; ++i) {
-                    const f32x2 v = *(const f32x2*)(ws + (((long long)n * SP + i) * C + cc) * 2);
-                    a1 += v[0]; a2 += v[1];
-                }
-                red[0][threadIdx.x] = a1;
-                red[1][threadIdx.x] = a2;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < VN; ++k) { t1[k] = red[0][vid * VN + k]; t2[k] = red[1][vid * VN + k]; }
+            split_sum<VN>(ws, red, n, SP, C, cg0, CG, vid, t1, t2);
         } else {
             // MODE 3: `ws` holds the conv epilogue's per-slot (mean, centred sum of squares) of equal-sized pixel groups
             // (p2p_igemm stat_part, nslots groups per image): pooled mean and variance by the parallel-variance rule,
@@ -422,19 +517,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
                 t2[k] = red[1][vid * VN + k];
             }
         }
-#pragma unroll
-        for (int k = 0; k < VN; ++k) {
-            float m = t1[k] / (float)HW;
-            float var = fmaxf(t2[k] / (float)HW - m * m, 0.f);
-            mu[k] = sh[k] + m;
-            rs[k] = rsqrtf(var + eps);
-            ga[k] = gamma[c + k];
-            be[k] = beta[c + k];
-            if (pr == 0 && sp == 0) {
-                stats[((long long)n * C + c + k) * 2 + 0] = mu[k];
-                stats[((long long)n * C + c + k) * 2 + 1] = rs[k];
-            }
-        }
+        coef_from_sums<VN>(t1, t2, sh, HW, eps, gamma, beta, stats, pr == 0 && sp == 0, n, C, c, co);
     }
     if (raw_kind == 1 && !raw_out) {
         // Dense input in the activation type (every launch of a bf16 step): U pixels per trip, every load of the trip issued
@@ -452,7 +535,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
                 if (p < pe) {
                     const long long e = base + (long long)p * C;
                     xr[u] = *(const vec_t*)((const T*)raw + e);
-                    if (mask) mk[u] = VN == 8 ? *(const unsigned long long*)(mask + e) : (unsigned long long)*(const unsigned*)(mask + e);
+                    if (mask) mk[u] = mask_vload<VN>(mask + e);
                     if (do_tail) {
                         const int yy = p / W, xx = p - yy * W;
                         tr[u] = *(const vec_t*)((const T*)tail.ptr + tail.off(n, yy, xx));
@@ -465,23 +548,18 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
                 if (p >= pe) continue;
                 vec_t o;
 #pragma unroll
-                for (int k = 0; k < VN; ++k) {
+                for (int k = 0; k < VN; ++k)
+                {
                     const float xv = to_f32((T)xr[u][k]);
-                    float y = gamma ? (xv - mu[k]) * rs[k] * ga[k] + be[k] : xv;
-                    if (mask) y *= ((mk[u] >> (8 * k)) & 0xff) ? 2.f : 0.f;
-                    if (act == P2P_ACT_LEAKY) y = y > 0.f ? y : alpha * y;
-                    else if (act == P2P_ACT_RELU) y = y > 0.f ? y : 0.f;
-                    o[k] = from_f32<T>(y);
+                    const float y = gamma ? norm_affine(xv, co.mu[k], co.rs[k], co.ga[k], co.be[k]) : xv;
+                    o[k] = from_f32<T>(drop_act(y, mask, mask ? mask_keep(mk[u], k) : 1.f, act, alpha));
                 }
                 const int yy = p / W, xx = p - yy * W;
                 T* op = (T*)out.ptr + out.off(n, yy, xx);
                 *(vec_t*)(op + c) = o;
-                // tail: the channels that follow this layer's slice in the concat buffer are copied by the lane that wrote the
-                // slice's last vector, so the pixel leaves the wave complete (no partially written 32-byte sectors in HBM)
-                if (do_tail) {
+                if (do_tail) {      // (the first tail vector's load went out with the trip's other loads)
                     *(vec_t*)(op + C) = tr[u];
-                    for (int t = 1; t < tail_vecs; ++t)
-                        *(vec_t*)(op + C + t * VN) = *(const vec_t*)((const T*)tail.ptr + tail.off(n, yy, xx) + t * VN);
+                    tail_copy<T>(op + C, (const T*)tail.ptr + tail.off(n, yy, xx), 1, tail_vecs);
                 }
             }
         }
@@ -492,27 +570,16 @@ __global__ __launch_bounds__(256) void norm_act_fwd_vec(int H, int W, int C, int
         float x[VN], keep[VN];
         raw_vload<T>(raw, raw_kind, nslabs, slab, e, x);
         if (raw_out) vstore<T>(raw_out + e, x);
-        if (mask) mask_vload8(mask + e, keep, VN);
+        if (mask) mask_vkeep<VN>(mask + e, keep);
 #pragma unroll
         for (int k = 0; k < VN; ++k) {
-            float y = gamma ? (x[k] - mu[k]) * rs[k] * ga[k] + be[k] : x[k];
-            if (mask) y *= keep[k];
-            if (act == P2P_ACT_LEAKY) y = y > 0.f ? y : alpha * y;
-            else if (act == P2P_ACT_RELU) y = y > 0.f ? y : 0.f;
-            x[k] = y;
+            const float y = gamma ? norm_affine(x[k], co.mu[k], co.rs[k], co.ga[k], co.be[k]) : x[k];
+            x[k] = drop_act(y, mask, mask ? keep[k] : 1.f, act, alpha);
         }
         int yy = p / W, xx = p - yy * W;
-        vstore<T>((T*)out.ptr + out.off(n, yy, xx) + c, x);
-        // tail: the channels that follow this layer's slice in the concat buffer are copied by the lane that wrote the
-        // slice's last vector, so the pixel leaves the wave complete (no partially written 32-byte sectors in HBM)
-        if (tail_vecs && c + VN == C) {
-            const long long to = tail.off(n, yy, xx), oo = out.off(n, yy, xx) + C;
-            for (int t = 0; t < tail_vecs; ++t) {
-                float tv[VN];
-                vload<T>((const T*)tail.ptr + to + t * VN, tv);
-                vstore<T>((T*)out.ptr + oo + t * VN, tv);
-            }
-        }
+        T* op = (T*)out.ptr + out.off(n, yy, xx);
+        vstore<T>(op + c, x);
+        if (tail_vecs && c + VN == C) tail_copy<T>(op + C, (const T*)tail.ptr + tail.off(n, yy, xx), 0, tail_vecs);
     }
 }
 
@@ -528,22 +595,15 @@ __global__ __launch_bounds__(256) void norm_act_bwd_vec(int H, int W, int C, int
     const int n = blockIdx.x;
     const int cg0 = blockIdx.y * CG;
     const int SP = gridDim.z, sp = blockIdx.z;
-    const int VPP = CG / VN, PR = 256 / VPP;
-    const int vid = threadIdx.x % VPP, pr = threadIdx.x / VPP;
-    const int c = cg0 + vid * VN;
+    const WgGeom<VN> wg(CG, cg0);
+    const int PR = wg.PR, vid = wg.vid, pr = wg.pr, c = wg.c;
     const int HW = H * W;
     const int chunk = (HW + SP - 1) / SP;
     const int pb = sp * chunk, pe = min(HW, pb + chunk);
     const long long pix0 = (long long)n * HW;
     const long long base = pix0 * C + c;
-    float mu[VN], rs[VN], ga[VN], be[VN];
-#pragma unroll
-    for (int k = 0; k < VN; ++k) {
-        mu[k] = stats[((long long)n * C + c + k) * 2 + 0];
-        rs[k] = stats[((long long)n * C + c + k) * 2 + 1];
-        ga[k] = gamma[c + k];
-        be[k] = beta[c + k];
-    }
+    Coef<VN> co;
+    coef_load<VN>(stats, gamma, beta, n, C, c, co);
     // d(yhat) and xhat of one pixel
     auto dyhat = [&](int p, float* d, float* xh) {
         long long e = base + (long long)p * C;
@@ -551,17 +611,11 @@ __global__ __launch_bounds__(256) void norm_act_bwd_vec(int H, int W, int C, int
         vload<T>(raw + e, x);
         gsrc_vload<T>(g1, pix0 + p, c, a1);
         gsrc_vload<T>(g2, pix0 + p, c, a2);
-        if (mask) mask_vload8(mask + e, keep, VN);
+        if (mask) mask_vkeep<VN>(mask + e, keep);
 #pragma unroll
         for (int k = 0; k < VN; ++k) {
-            xh[k] = (x[k] - mu[k]) * rs[k];
-            float a = xh[k] * ga[k] + be[k];
-            float kp = mask ? keep[k] : 1.f;
-            a *= kp;
-            float slope = 1.f;
-            if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
-            else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
-            d[k] = (a1[k] + a2[k]) * slope * kp;
+            xh[k] = norm_xhat(x[k], co.mu[k], co.rs[k]);
+            d[k] = bwd_elem(true, xh[k], co.ga[k], co.be[k], mask ? keep[k] : 1.f, a1[k] + a2[k], act, alpha);
         }
     };
     float t1[VN], t2[VN];
@@ -577,29 +631,14 @@ __global__ __launch_bounds__(256) void norm_act_bwd_vec(int H, int W, int C, int
         }
         col_reduce2<VN>(red, CG, PR, vid, pr, s1, s2, t1, t2);
         if (MODE == 1) {
-            if (pr == 0)
-#pragma unroll
-                for (int k = 0; k < VN; ++k) {
-                    ws[(((long long)n * SP + sp) * C + c + k) * 2 + 0] = t1[k];
-                    ws[(((long long)n * SP + sp) * C + c + k) * 2 + 1] = t2[k];
-                }
+            if (pr == 0) split_store<VN>(ws, n, SP, sp, C, c, t1, t2);
             return;
         }
     } else {
-        if (threadIdx.x < CG) {
-            const int cc = cg0 + threadIdx.x;
-            float a1 = 0.f, a2 = 0.f;
-            for (int i = 0; i < SP; ++i) {
-                const f32x2 v = *(const f32x2*)(ws + (((long long)n * SP + i) * C + cc) * 2);
-                a1 += v[0]; a2 += v[1];
-            }
-            red[0][threadIdx.x] = a1;
-            red[1][threadIdx.x] = a2;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < VN; ++k) { t1[k] = red[0][vid * VN + k]; t2[k] = red[1][vid * VN + k]; }
+        split_sum<VN>(ws, red, n, SP, C, cg0, CG, vid, t1, t2);
     }
+    // (this block is written out here and in norm_act_bwd_reg, not shared: as a helper it compiled to other stores and a second
+    // copy of the divisions, and the c2 launches of norm_act_bwd_reg<bf16, 8, 0> went 53 -> 57 ... 62 us)
     float m1[VN], m2[VN];
 #pragma unroll
     for (int k = 0; k < VN; ++k) {
@@ -614,21 +653,31 @@ __global__ __launch_bounds__(256) void norm_act_bwd_vec(int H, int W, int C, int
         float d[VN], xh[VN];
         dyhat(p, d, xh);
 #pragma unroll
-        for (int k = 0; k < VN; ++k) d[k] = ga[k] * rs[k] * (d[k] - m1[k] - xh[k] * m2[k]);
+        for (int k = 0; k < VN; ++k) d[k] = bwd_dx(co.ga[k], co.rs[k], d[k], m1[k], xh[k], m2[k]);
         int yy = p / W, xx = p - yy * W;
         vstore<T>((T*)draw.ptr + draw.off(n, yy, xx) + c, d);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Block order of the register-resident forms below (backward and forward): the channel groups of one image sit on ONE XCD, next to
+// each other in dispatch order (workgroup id = ((n / 8) * groups + group) * 8 + n % 8): with groups narrower than a 128-byte line
+// the line's other readers find it in that XCD's L2.  The grid is padded to whole eights of images (reg_grid): n may be >= N.
+__device__ __forceinline__ void reg_block(int C, int CG, int& n, int& cg0) {
+    const int ncg = C / CG;
+    const int lin = blockIdx.x;
+    n = ((lin >> 3) / ncg) * 8 + (lin & 7);
+    cg0 = ((lin >> 3) % ncg) * CG;
+}
+static inline unsigned reg_grid(int N, int C, int CG) { return (unsigned)(((N + 7) / 8) * 8 * (C / CG)); }
+
 // Register-resident form (r05): one launch, every operand read ONCE.  A workgroup owns (image, CG channels) like MODE 0 above,
 // but a thread keeps its <= PPL pixels (x packed in the storage type, d(yhat) in f32) in registers between the reduction and
 // the apply pass instead of reading them again, and all of its loads are issued before the first use.  Geometry (host side,
 // norm_bwd_reg_geom): the widest channel group whose pixel rows fit PPL <= 8 and that still yields
 // >= 512 workgroups, else the narrowest one -- at batch 4 a 16x16x128 tensor becomes 64 workgroups of one pixel per thread
-// instead of 16 workgroups looping twice over 16 pixels (c1: 29 us for two launches -> one launch-sized kernel).  The channel
-// groups of one image sit on ONE XCD, next to each other in dispatch order (workgroup id = ((n / 8) * groups + group) * 8 + n % 8):
-// with groups narrower than a 128-byte line the line's other readers find it in that XCD's L2.
+// instead of 16 workgroups looping twice over 16 pixels (c1: 29 us for two launches -> one launch-sized kernel).  Block order:
+// reg_block above.
 template <typename T, int PPL, int SLABS>
 __global__ __launch_bounds__(256) void norm_act_bwd_reg(int N, int HW, int W, int C, int CG, const T* __restrict__ raw,
                                                         const float* __restrict__ stats, const float* __restrict__ gamma,
@@ -638,23 +687,15 @@ __global__ __launch_bounds__(256) void norm_act_bwd_reg(int N, int HW, int W, in
     constexpr int VN = VecOf<T>::N;
     typedef typename VecOf<T>::type vec_t;
     __shared__ __attribute__((aligned(16))) float red[2][2048];
-    const int ncg = C / CG;
-    const int lin = blockIdx.x;
-    const int n = ((lin >> 3) / ncg) * 8 + (lin & 7), cg0 = ((lin >> 3) % ncg) * CG;
+    int n, cg0;
+    reg_block(C, CG, n, cg0);
     if (n >= N) return;                                  // (whole workgroup: the grid is padded to 8 images)
-    const int VPP = CG / VN, PR = 256 / VPP;
-    const int vid = threadIdx.x % VPP, pr = threadIdx.x / VPP;
-    const int c = cg0 + vid * VN;
+    const WgGeom<VN> wg(CG, cg0);
+    const int PR = wg.PR, vid = wg.vid, pr = wg.pr, c = wg.c;
     const long long pix0 = (long long)n * HW;
     const long long base = pix0 * C + c;
-    float mu[VN], rs[VN], ga[VN], be[VN];
-#pragma unroll
-    for (int k = 0; k < VN; ++k) {
-        mu[k] = stats[((long long)n * C + c + k) * 2 + 0];
-        rs[k] = stats[((long long)n * C + c + k) * 2 + 1];
-        ga[k] = gamma[c + k];
-        be[k] = beta[c + k];
-    }
+    Coef<VN> co;
+    coef_load<VN>(stats, gamma, beta, n, C, c, co);
     vec_t xr[PPL];
     float d[PPL][VN];
     float s1[VN], s2[VN];
@@ -669,17 +710,11 @@ __global__ __launch_bounds__(256) void norm_act_bwd_reg(int N, int HW, int W, in
             xr[i] = *(const vec_t*)(raw + e);
             gsrc_vload<T, SLABS>(g1, pix0 + p, c, a1);
             gsrc_vload<T, SLABS>(g2, pix0 + p, c, a2);
-            if (mask) mask_vload8(mask + e, keep, VN);
+            if (mask) mask_vkeep<VN>(mask + e, keep);
 #pragma unroll
             for (int k = 0; k < VN; ++k) {
-                const float xh = (to_f32((T)xr[i][k]) - mu[k]) * rs[k];
-                float a = xh * ga[k] + be[k];
-                const float kp = mask ? keep[k] : 1.f;
-                a *= kp;
-                float slope = 1.f;
-                if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
-                else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
-                d[i][k] = (a1[k] + a2[k]) * slope * kp;
+                const float xh = norm_xhat(to_f32((T)xr[i][k]), co.mu[k], co.rs[k]);
+                d[i][k] = bwd_elem(true, xh, co.ga[k], co.be[k], mask ? keep[k] : 1.f, a1[k] + a2[k], act, alpha);
                 s1[k] += d[i][k];
                 s2[k] += d[i][k] * xh;
             }
@@ -707,8 +742,8 @@ __global__ __launch_bounds__(256) void norm_act_bwd_reg(int N, int HW, int W, in
         float r[VN];
 #pragma unroll
         for (int k = 0; k < VN; ++k) {
-            const float xh = (to_f32((T)xr[i][k]) - mu[k]) * rs[k];
-            r[k] = ga[k] * rs[k] * (d[i][k] - m1[k] - xh * m2[k]);
+            const float xh = norm_xhat(to_f32((T)xr[i][k]), co.mu[k], co.rs[k]);
+            r[k] = bwd_dx(co.ga[k], co.rs[k], d[i][k], m1[k], xh, m2[k]);
         }
         const int yy = p / W, xx = p - yy * W;
         vstore<T>((T*)draw.ptr + draw.off(n, yy, xx) + c, r);
@@ -752,13 +787,11 @@ __global__ __launch_bounds__(256) void norm_act_fwd_reg(int N, int HW, int W, in
                                                         T* __restrict__ raw_out, float* __restrict__ stats) {
     constexpr int VN = VecOf<T>::N;
     __shared__ __attribute__((aligned(16))) float red[2][2048];
-    const int ncg = C / CG;
-    const int lin = blockIdx.x;
-    const int n = ((lin >> 3) / ncg) * 8 + (lin & 7), cg0 = ((lin >> 3) % ncg) * CG;
+    int n, cg0;
+    reg_block(C, CG, n, cg0);
     if (n >= N) return;
-    const int VPP = CG / VN, PR = 256 / VPP;
-    const int vid = threadIdx.x % VPP, pr = threadIdx.x / VPP;
-    const int c = cg0 + vid * VN;
+    const WgGeom<VN> wg(CG, cg0);
+    const int PR = wg.PR, vid = wg.vid, pr = wg.pr, c = wg.c;
     const long long base = (long long)n * HW * C + c;
     float x[PPL][VN], sh[VN], s1[VN], s2[VN];
     unsigned long long mk[PPL];
@@ -770,7 +803,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_reg(int N, int HW, int W, in
         if (p < HW) {
             const long long e = base + (long long)p * C;
             raw_vload<T, SLABS>(raw, raw_kind, nslabs, slab, e, x[i]);
-            if (mask) mk[i] = VN == 8 ? *(const unsigned long long*)(mask + e) : (unsigned long long)*(const unsigned*)(mask + e);
+            if (mask) mk[i] = mask_vload<VN>(mask + e);
         } else {
 #pragma unroll
             for (int k = 0; k < VN; ++k) x[i][k] = 0.f;
@@ -783,21 +816,10 @@ __global__ __launch_bounds__(256) void norm_act_fwd_reg(int N, int HW, int W, in
         if (pr + i * PR < HW)
 #pragma unroll
             for (int k = 0; k < VN; ++k) { const float d = x[i][k] - sh[k]; s1[k] += d; s2[k] += d * d; }
-    float t1[VN], t2[VN], mu[VN], rs[VN], ga[VN], be[VN];
+    float t1[VN], t2[VN];
+    Coef<VN> co;
     col_reduce2<VN, VN == 4>(red, CG, PR, vid, pr, s1, s2, t1, t2);       // f32: trees (see col_reduce2); bf16 inputs leave the sums room
-#pragma unroll
-    for (int k = 0; k < VN; ++k) {
-        const float m = t1[k] / (float)HW;
-        const float var = fmaxf(t2[k] / (float)HW - m * m, 0.f);
-        mu[k] = sh[k] + m;
-        rs[k] = rsqrtf(var + eps);
-        ga[k] = gamma[c + k];
-        be[k] = beta[c + k];
-        if (pr == 0) {
-            stats[((long long)n * C + c + k) * 2 + 0] = mu[k];
-            stats[((long long)n * C + c + k) * 2 + 1] = rs[k];
-        }
-    }
+    coef_from_sums<VN>(t1, t2, sh, HW, eps, gamma, beta, stats, pr == 0, n, C, c, co);
 #pragma unroll
     for (int i = 0; i < PPL; ++i) {
         const int p = pr + i * PR;
@@ -805,13 +827,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_reg(int N, int HW, int W, in
         if (raw_out) vstore<T>(raw_out + base + (long long)p * C, x[i]);
         float y[VN];
 #pragma unroll
-        for (int k = 0; k < VN; ++k) {
-            float v = (x[i][k] - mu[k]) * rs[k] * ga[k] + be[k];
-            if (mask) v *= ((mk[i] >> (8 * k)) & 0xff) ? 2.f : 0.f;
-            if (act == P2P_ACT_LEAKY) v = v > 0.f ? v : alpha * v;
-            else if (act == P2P_ACT_RELU) v = v > 0.f ? v : 0.f;
-            y[k] = v;
-        }
+        for (int k = 0; k < VN; ++k) y[k] = fwd_elem(x[i][k], co.mu[k], co.rs[k], co.ga[k], co.be[k], mask, mask_keep(mk[i], k), act, alpha);
         const int yy = p / W, xx = p - yy * W;
         vstore<T>((T*)out.ptr + out.off(n, yy, xx) + c, y);
     }
@@ -877,14 +893,13 @@ __global__ __launch_bounds__(256) void norm_act_fwd_small(int HW, int W, int C, 
         const long long e = base + (long long)p * C;
         float keep[VN], y[VN];
         if (raw_out) vstore<T>(raw_out + e, x[i]);
-        if (mask) mask_vload8(mask + e, keep, VN);
+        if (mask) mask_vkeep<VN>(mask + e, keep);
 #pragma unroll
         for (int k = 0; k < VN; ++k) {
-            float v = gamma ? (x[i][k] - mu[k]) * rs[k] * gamma[c + k] + beta[c + k] : x[i][k];
-            if (mask) v *= keep[k];
-            if (act == P2P_ACT_LEAKY) v = v > 0.f ? v : alpha * v;
-            else if (act == P2P_ACT_RELU) v = v > 0.f ? v : 0.f;
-            y[k] = v;
+            // gamma and beta are read at their use, pixel by pixel: held in registers from the statistics on (as the other forms do)
+            // they cost the bf16 instantiations a wave of occupancy (56 -> 70 and 78 -> 90 VGPRs)
+            const float v = gamma ? norm_affine(x[i][k], mu[k], rs[k], gamma[c + k], beta[c + k]) : x[i][k];
+            y[k] = drop_act(v, mask, mask ? keep[k] : 1.f, act, alpha);
         }
         const int yy = p / W, xx = p - yy * W;
         vstore<T>((T*)out.ptr + out.off(n, yy, xx) + c, y);
@@ -906,14 +921,8 @@ __global__ __launch_bounds__(256) void norm_act_bwd_small(int HW, int W, int C, 
     const int cvn = C / VN;
     const int n = (int)(item / cvn), c = (int)(item - (long long)n * cvn) * VN;
     const long long pix0 = (long long)n * HW, base = pix0 * C + c;
-    float mu[VN], rs[VN], ga[VN], be[VN];
-#pragma unroll
-    for (int k = 0; k < VN; ++k) {
-        mu[k] = stats[((long long)n * C + c + k) * 2 + 0];
-        rs[k] = stats[((long long)n * C + c + k) * 2 + 1];
-        ga[k] = gamma[c + k];
-        be[k] = beta[c + k];
-    }
+    Coef<VN> co;
+    coef_load<VN>(stats, gamma, beta, n, C, c, co);
     float d[PPL][VN], xh[PPL][VN];
 #pragma unroll
     for (int i = 0; i < PPL; ++i) {
@@ -924,17 +933,11 @@ __global__ __launch_bounds__(256) void norm_act_bwd_small(int HW, int W, int C, 
             vload<T>(raw + e, x);
             gsrc_vload<T, SLABS>(g1, pix0 + p, c, a1);
             gsrc_vload<T, SLABS>(g2, pix0 + p, c, a2);
-            if (mask) mask_vload8(mask + e, keep, VN);
+            if (mask) mask_vkeep<VN>(mask + e, keep);
 #pragma unroll
             for (int k = 0; k < VN; ++k) {
-                xh[i][k] = (x[k] - mu[k]) * rs[k];
-                float a = xh[i][k] * ga[k] + be[k];
-                const float kp = mask ? keep[k] : 1.f;
-                a *= kp;
-                float slope = 1.f;
-                if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
-                else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
-                d[i][k] = (a1[k] + a2[k]) * slope * kp;
+                xh[i][k] = norm_xhat(x[k], co.mu[k], co.rs[k]);
+                d[i][k] = bwd_elem(true, xh[i][k], co.ga[k], co.be[k], mask ? keep[k] : 1.f, a1[k] + a2[k], act, alpha);
             }
         } else {
 #pragma unroll
@@ -961,7 +964,7 @@ __global__ __launch_bounds__(256) void norm_act_bwd_small(int HW, int W, int C, 
         if (p >= HW) continue;
         float r[VN];
 #pragma unroll
-        for (int k = 0; k < VN; ++k) r[k] = ga[k] * rs[k] * (d[i][k] - m1[k] - xh[i][k] * m2[k]);
+        for (int k = 0; k < VN; ++k) r[k] = bwd_dx(co.ga[k], co.rs[k], d[i][k], m1[k], xh[i][k], m2[k]);
         const int yy = p / W, xx = p - yy * W;
         vstore<T>((T*)draw.ptr + draw.off(n, yy, xx) + c, r);
     }
@@ -1020,7 +1023,8 @@ extern "C" int p2p_colsum_batched(const float* part, const int* table, int ntask
 }
 
 // Backward of a bare activation whose OUTPUT is stored (LeakyReLU fused into the conv epilogue of down1 / D.down,
-// networks.py:19,46,58): sign(out) == sign(pre-activation), so d(pre) = (g1 + g2) * (out > 0 ? 1 : alpha).
+// networks.py:19,46,58): sign(out) == sign(pre-activation), so d(pre) = (g1 + g2) * (out > 0 ? 1 : alpha).  (Always LeakyReLU,
+// no `act` argument, and g passes through unmultiplied where out > 0: not an act_slope ladder.)
 template <typename T>
 __global__ void act_bwd_kernel(int N, int H, int W, int C, TView actv, GSrc g1, GSrc g2, float alpha, TView draw) {
     long long total = (long long)N * H * W * C;
@@ -1057,17 +1061,19 @@ __global__ void act_bwd_vec_kernel(int N, int H, int W, int C, TView actv, GSrc 
     }
 }
 
+// May gsrc_vload read this gradient source with whole 16-byte vectors of vn values?
+static bool gsrc_vec_ok(const p2p_gsrc* g, int vn) {
+    if (!g || !g->ptr || g->kind != 1) return true;     // f32 slabs are read element-wise unless they are aligned
+    return g->ld % vn == 0 && g->coff % vn == 0 && ((uintptr_t)g->ptr % 16) == 0;
+}
+
 extern "C" int p2p_act_bwd(int dtype, int N, int H, int W, int C, const p2p_tensor* act_out, const p2p_gsrc* g1,
                            const p2p_gsrc* g2, float alpha, const p2p_tensor* draw, void* stream) {
     P2P_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && act_out && act_out->ptr && g1 && draw && draw->ptr, "p2p_act_bwd: bad args");
     {
         const int esz = dtype == P2P_BF16 ? 2 : 4, vn = 16 / esz;
-        auto gs_ok = [&](const p2p_gsrc* g) {
-            if (!g || !g->ptr || g->kind == 0) return true;
-            return g->kind != 1 || (g->ld % vn == 0 && g->coff % vn == 0 && ((uintptr_t)g->ptr % 16) == 0);
-        };
         if (C % 8 == 0 && act_out->ld % vn == 0 && draw->ld % vn == 0 && ((uintptr_t)act_out->ptr % 16) == 0 &&
-            ((uintptr_t)draw->ptr % 16) == 0 && gs_ok(g1) && gs_ok(g2)) {
+            ((uintptr_t)draw->ptr % 16) == 0 && gsrc_vec_ok(g1, vn) && gsrc_vec_ok(g2, vn)) {
             long long tv = (long long)N * H * W * (C / vn);
             long long bl = (tv + 255) / 256;
             if (bl > 8192) bl = 8192;
@@ -1104,8 +1110,62 @@ static int norm_route_code(const NormRoute& r) {
     return P2P_NORM_ROUTE(r.form, r.ppl, r.slabs, lg);
 }
 
-// vec: whole 16-byte vectors everywhere; nsplit as passed (with its | 0x100 / | 0x200 flags)
-static NormRoute norm_fwd_route(int N, int HW, int C, int vn, bool vec, bool has_gamma, bool has_tail, int raw_kind, int nsplit,
+// The `nsplit` argument of p2p_norm_act_fwd / p2p_norm_act_bwd, decoded (this is the only place that knows its encoding):
+//   > 0: pixel splits wanted in the low byte, | 0x100 and | 0x200 as below;  < 0: -nsplit statistics slots per image in ws (forward)
+struct NSplit {
+    int sp;          // pixel splits asked for (>= 1)
+    // | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only -- their order of sums does not depend on N, and the
+    // parity gate (tests/test_train_step_gpu.py, 1e-4 on every gradient tensor at batch 2) holds only while no ReLU gate flips against
+    // the f64 oracle: a forward pass that rounds differently by a few ulp flips one (a 1e-2 error on a weight gradient)
+    bool two_pass;
+    bool geom256;    // | 0x200: the register-resident geometry of batch 256 (tests)
+    int nslots;      // statistics slots per image that the conv epilogue left in ws, 0 = none
+};
+static NSplit nsplit_decode(int nsplit) {
+    NSplit s = {1, false, false, 0};
+    if (nsplit > 0) {
+        s.sp = (nsplit & 0xff) < 1 ? 1 : (nsplit & 0xff);
+        s.two_pass = (nsplit & 0x100) != 0;
+        s.geom256 = (nsplit & 0x200) != 0;
+    } else if (nsplit < 0) {
+        s.nslots = -nsplit;
+    }
+    return s;
+}
+
+// Channel group of the workgroup ("vec") forms: the widest one <= 64 that divides C in whole vectors of vn channels; 0 when its
+// vectors do not divide the 256 threads into whole pixel rows (the form does not serve such a C)
+static int vec_cg(int C, int vn) {
+    int CG = C > 64 ? 64 : C;
+    while (C % CG) CG -= vn;
+    return 256 % (CG / vn) == 0 ? CG : 0;
+}
+
+// Run-time (ppl, slabs) of a route -> the template arguments of its kernel: calls f(integral_constant<PPL>, integral_constant<SLABS>)
+// with PPL in {1, 2, 4, ... MAXPPL} (anything else: MAXPPL) and SLABS = 4 / 0 (see raw_vload), so a launch is written once.
+template <int V> using ic = std::integral_constant<int, V>;
+template <typename F>
+static void dispatch_slabs(bool slabs, F&& f) {
+    if (slabs) f(ic<4>{}); else f(ic<0>{});
+}
+template <int MAXPPL, typename F>
+static void dispatch_ppl_slabs(int ppl, bool slabs, F&& f) {
+    dispatch_slabs(slabs, [&](auto S) {
+        if (ppl == 1) f(ic<1>{}, S);
+        else if (ppl == 2) f(ic<2>{}, S);
+        else if (MAXPPL == 4 || ppl == 4) f(ic<4>{}, S);
+        else if constexpr (MAXPPL == 8) f(ic<8>{}, S);
+    });
+}
+// `last`: the launch may carry the entry point's stop event (P2P_LAUNCH_LAST)
+template <typename K, typename... A>
+static void launch256(bool last, K kernel, dim3 grid, hipStream_t st, A... args) {
+    if (last) P2P_LAUNCH_LAST(kernel, grid, dim3(256), 0, st, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, args...);
+}
+
+// vec: whole 16-byte vectors everywhere
+static NormRoute norm_fwd_route(int N, int HW, int C, int vn, bool vec, bool has_gamma, bool has_tail, int raw_kind, const NSplit& ns,
                                 bool has_ws, long long ws_bytes) {
     NormRoute r = {P2P_NORM_FORM_SCALAR, 0, 0, 0, 1, 0};
     if (vec && HW <= 16) {
@@ -1116,36 +1176,25 @@ static NormRoute norm_fwd_route(int N, int HW, int C, int vn, bool vec, bool has
         small_geom(HW, r.lgG, r.ppl);
         return r;
     }
-    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only -- their order of sums does not depend on N,
-    // and the parity gate (tests/test_train_step_gpu.py, 1e-4 on every gradient tensor at batch 2) holds only while no ReLU gate
-    // flips against the f64 oracle: a forward pass that rounds differently by a few ulp flips one (a 1e-2 error on a weight gradient)
-    const bool legacy = nsplit > 0 && (nsplit & 0x100);
-    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
-    if (nsplit > 0) nsplit &= 0xff;
-    if (vec && has_gamma && !has_tail && nsplit >= 0 && !legacy) {
+    if (vec && has_gamma && !has_tail && !ns.nslots && !ns.two_pass) {
         int ppl = 0;
-        const int rcg = norm_bwd_reg_geom(n_geom, HW, C, vn, ppl, true);
+        const int rcg = norm_bwd_reg_geom(ns.geom256 ? 256 : N, HW, C, vn, ppl, true);
         if (rcg) {
             r.form = P2P_NORM_FORM_REG; r.cg = rcg; r.ppl = ppl; r.slabs = raw_kind == 2;
             return r;
         }
     }
-    if (vec) {
-        int CG = C > 64 ? 64 : C;
-        while (C % CG) CG -= vn;
-        const int vpp = CG / vn;
-        if (256 % vpp == 0) {
-            const int prr = 256 / vpp;
-            int sp = nsplit < 1 ? 1 : nsplit;
-            while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;       // every split keeps all pixel lanes busy
-            r.cg = CG;
-            // statistics were produced by the conv epilogue (-nsplit slots per image in ws): apply only
-            if (nsplit < 0 && has_gamma && has_ws) { r.form = P2P_NORM_FORM_VEC3; return r; }
-            if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = has_gamma ? 1 : sp;
-            r.sp = sp;
-            r.form = (sp == 1 || !has_gamma) ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
-            return r;
-        }
+    const int CG = vec ? vec_cg(C, vn) : 0;
+    if (CG) {
+        const int prr = 256 / (CG / vn);
+        int sp = ns.sp;
+        while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;       // every split keeps all pixel lanes busy
+        r.cg = CG;
+        // statistics were produced by the conv epilogue (ns.nslots slots per image in ws): apply only
+        if (ns.nslots && has_gamma && has_ws) { r.form = P2P_NORM_FORM_VEC3; return r; }
+        if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = has_gamma ? 1 : sp;
+        r.sp = sp;
+        r.form = (sp == 1 || !has_gamma) ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
     }
     return r;
 }
@@ -1169,11 +1218,10 @@ static int norm_act_fwd_impl(int dtype, int N, int H, int W, int C, const void* 
         // the tail copy lives in the workgroup form only (the caller asks for it on wide maps: the last skip connection)
         P2P_REQUIRE(tail->ptr && tail_ch > 0 && tail_ch % vn == 0 && tail->ld % vn == 0 && ((uintptr_t)tail->ptr % 16) == 0,
                     "p2p_norm_act_fwd_tail: the tail must be whole 16-byte vectors");
-        int cgt = C > 64 ? 64 : C;
-        while (C % cgt) cgt -= vn;
-        P2P_REQUIRE(vec && H * W > 16 && 256 % (cgt / vn) == 0, "p2p_norm_act_fwd_tail: shape not served by the vector form");
+        P2P_REQUIRE(vec && H * W > 16 && vec_cg(C, vn), "p2p_norm_act_fwd_tail: shape not served by the vector form");
     }
-    const NormRoute r = norm_fwd_route(N, H * W, C, vn, vec, gamma != nullptr, tail != nullptr, raw_kind, nsplit, ws != nullptr, ws_bytes);
+    const NSplit ns = nsplit_decode(nsplit);
+    const NormRoute r = norm_fwd_route(N, H * W, C, vn, vec, gamma != nullptr, tail != nullptr, raw_kind, ns, ws != nullptr, ws_bytes);
     if (route_out) { *route_out = norm_route_code(r); return 0; }      // the host query: nothing started
     hipStream_t st = (hipStream_t)stream;
     if (r.form == P2P_NORM_FORM_SMALL) {
@@ -1181,57 +1229,41 @@ static int norm_act_fwd_impl(int dtype, int N, int H, int W, int C, const void* 
         const long long items = (long long)N * (C / vn);
         const long long threads = items << lgG;
         const dim3 grid((unsigned)((threads + 255) / 256));
-#define NF_SMALL2(P_, S_) norm_act_fwd_small<T, P_, S_><<<grid, 256, 0, st>>>(H * W, W, C, lgG, items, raw, raw_kind, nslabs, slab_stride, gamma, \
-                                                                   beta, eps, act, alpha, mask, make_view(out), (T*)raw_out, stats)
-#define NF_SMALL(P_) do { if (r.slabs) NF_SMALL2(P_, 4); else NF_SMALL2(P_, 0); } while (0)
-        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(1)); }
-        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(2)); }
-        else { P2P_DISPATCH_DTYPE(dtype, NF_SMALL(4)); }
-#undef NF_SMALL
-#undef NF_SMALL2
+        P2P_DISPATCH_DTYPE(dtype, (dispatch_ppl_slabs<4>(r.ppl, r.slabs, [&](auto P, auto S) {
+            norm_act_fwd_small<T, decltype(P)::value, decltype(S)::value><<<grid, 256, 0, st>>>(
+                H * W, W, C, lgG, items, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask, make_view(out),
+                (T*)raw_out, stats);
+        })));
         return p2p_check_launch("p2p_norm_act_fwd");
     }
     if (r.form == P2P_NORM_FORM_REG) {
-        const int rcg = r.cg;
-        const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
-#define NF_REG2(P_, S_) norm_act_fwd_reg<T, P_, S_><<<grid, 256, 0, st>>>(N, H * W, W, C, rcg, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, \
-                                                                mask, make_view(out), (T*)raw_out, stats)
-#define NF_REG(P_) do { if (r.slabs) NF_REG2(P_, 4); else NF_REG2(P_, 0); } while (0)
-        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NF_REG(1)); }
-        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NF_REG(2)); }
-        else if (r.ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NF_REG(4)); }
-        else { P2P_DISPATCH_DTYPE(dtype, NF_REG(8)); }
-#undef NF_REG
-#undef NF_REG2
+        const dim3 grid(reg_grid(N, C, r.cg));
+        P2P_DISPATCH_DTYPE(dtype, (dispatch_ppl_slabs<8>(r.ppl, r.slabs, [&](auto P, auto S) {
+            norm_act_fwd_reg<T, decltype(P)::value, decltype(S)::value><<<grid, 256, 0, st>>>(
+                N, H * W, W, C, r.cg, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask, make_view(out),
+                (T*)raw_out, stats);
+        })));
         return p2p_check_launch("p2p_norm_act_fwd");
     }
-    if (r.form == P2P_NORM_FORM_VEC3) {
-        // the pixel range can be split freely for parallelism
-        const int CG = r.cg, prr = 256 / (CG / vn);
-        const int nslots = -nsplit;
-        int sp2 = 1;
-        while ((long long)N * (C / CG) * sp2 < 2048 && (H * W) / (sp2 * 2) >= prr && sp2 < 64) sp2 *= 2;
-        dim3 grid3(N, C / CG, sp2);
-        P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 3><<<grid3, 256, 0, st>>>(
-                                      H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                      make_view(out), (T*)raw_out, stats, ws, nslots, tv, tvecs)));
-        return p2p_check_launch("p2p_norm_act_fwd");
-    }
-    if (r.form == P2P_NORM_FORM_VEC0 || r.form == P2P_NORM_FORM_VEC12) {
+    if (r.form == P2P_NORM_FORM_VEC0 || r.form == P2P_NORM_FORM_VEC12 || r.form == P2P_NORM_FORM_VEC3) {
         const int CG = r.cg;
-        dim3 grid(N, C / CG, r.sp);
-        if (r.form == P2P_NORM_FORM_VEC0) {
-            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 0><<<grid, 256, 0, st>>>(
-                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
-        } else {
-            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 1><<<grid, 256, 0, st>>>(
-                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
-            P2P_DISPATCH_DTYPE(dtype, (norm_act_fwd_vec<T, 2><<<grid, 256, 0, st>>>(
-                                          H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask,
-                                          make_view(out), (T*)raw_out, stats, ws, 0, tv, tvecs)));
+        int sp = r.sp;
+        if (r.form == P2P_NORM_FORM_VEC3) {
+            // the statistics are there: the pixel range can be split freely for parallelism
+            const int prr = 256 / (CG / vn);
+            while ((long long)N * (C / CG) * sp < 2048 && (H * W) / (sp * 2) >= prr && sp < 64) sp *= 2;
         }
+        const dim3 grid(N, C / CG, sp);
+        P2P_DISPATCH_DTYPE(dtype, ([&] {
+            auto launch = [&](auto M) {
+                norm_act_fwd_vec<T, decltype(M)::value><<<grid, 256, 0, st>>>(
+                    H, W, C, CG, raw, raw_kind, nslabs, slab_stride, gamma, beta, eps, act, alpha, mask, make_view(out), (T*)raw_out,
+                    stats, ws, decltype(M)::value == 3 ? ns.nslots : 0, tv, tvecs);
+            };
+            if (r.form == P2P_NORM_FORM_VEC3) launch(ic<3>{});
+            else if (r.form == P2P_NORM_FORM_VEC0) launch(ic<0>{});
+            else { launch(ic<1>{}); launch(ic<2>{}); }
+        }()));
         return p2p_check_launch("p2p_norm_act_fwd");
     }
     int CB = pick_cb(C);
@@ -1277,7 +1309,7 @@ extern "C" int p2p_norm_act_fwd_tail(int dtype, int N, int H, int W, int C, cons
                              raw_out, stats, ws, ws_bytes, nsplit, tail, tail_ch, stream);
 }
 
-static NormRoute norm_bwd_route(int N, int HW, int C, int vn, bool vec, bool g_slabs, int nsplit, bool has_ws, long long ws_bytes) {
+static NormRoute norm_bwd_route(int N, int HW, int C, int vn, bool vec, bool g_slabs, const NSplit& ns, bool has_ws, long long ws_bytes) {
     NormRoute r = {P2P_NORM_FORM_SCALAR, 0, 0, 0, 1, 0};
     if (vec && HW <= 16) {
         r.form = P2P_NORM_FORM_SMALL;
@@ -1285,35 +1317,26 @@ static NormRoute norm_bwd_route(int N, int HW, int C, int vn, bool vec, bool g_s
         small_geom(HW, r.lgG, r.ppl);
         return r;
     }
-    // nsplit | 0x100 (the engine's f32 parity mode): the two-pass workgroup forms only (see norm_fwd_route)
-    const bool legacy = nsplit > 0 && (nsplit & 0x100);
-    const int n_geom = (nsplit > 0 && (nsplit & 0x200)) ? 256 : N;      // | 0x200: the register-resident geometry of batch 256 (tests)
-    if (nsplit > 0) nsplit &= 0xff;
-    if (vec && !legacy) {
+    if (vec && !ns.two_pass) {
         int ppl = 0;
-        const int rcg = norm_bwd_reg_geom(n_geom, HW, C, vn, ppl);
+        const int rcg = norm_bwd_reg_geom(ns.geom256 ? 256 : N, HW, C, vn, ppl);
         if (rcg) {
             r.form = P2P_NORM_FORM_REG; r.cg = rcg; r.ppl = ppl; r.slabs = g_slabs;
             return r;
         }
     }
-    if (vec) {
-        int CG = C > 64 ? 64 : C;
-        while (C % CG) CG -= vn;
+    int CG = vec ? vec_cg(C, vn) : 0;
+    if (CG) {
         // a pixel split was asked for, but 32-channel groups alone already give >= 1024 workgroups: take those and keep
         // the one-launch form (no second read of x and the gradient from HBM)
-        const bool narrow = nsplit > 1 && CG == 64 && C % 32 == 0 && (long long)N * (C / 32) >= 1024 && HW >= 64;
-        if (narrow) CG = 32;
-        const int vpp = CG / vn;
-        if (256 % vpp == 0) {
-            const int prr = 256 / vpp;
-            int sp = (nsplit < 1 || narrow) ? 1 : nsplit;
-            while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;
-            if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = 1;
-            r.cg = CG; r.sp = sp;
-            r.form = sp == 1 ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
-            return r;
-        }
+        const bool narrow = ns.sp > 1 && CG == 64 && C % 32 == 0 && (long long)N * (C / 32) >= 1024 && HW >= 64;
+        if (narrow) CG = 32;           // (32 / vn lanes per pixel divide 256 as well)
+        const int prr = 256 / (CG / vn);
+        int sp = narrow ? 1 : ns.sp;
+        while (sp > 1 && (HW + sp - 1) / sp < prr) sp >>= 1;
+        if (!has_ws || (long long)N * sp * C * 2 * 4 > ws_bytes) sp = 1;
+        r.cg = CG; r.sp = sp;
+        r.form = sp == 1 ? P2P_NORM_FORM_VEC0 : P2P_NORM_FORM_VEC12;
     }
     return r;
 }
@@ -1327,15 +1350,10 @@ static int norm_act_bwd_impl(int dtype, int N, int H, int W, int C, const void* 
     P2P_REQUIRE(raw && draw && draw->ptr && g1, "p2p_norm_act_bwd: null pointer");
     P2P_REQUIRE(!gamma || (stats && beta && dgamma_part && dbeta_part), "p2p_norm_act_bwd: norm needs stats/beta/partials");
     const int esz = dtype == P2P_BF16 ? 2 : 4, vn = 16 / esz;
-    auto gs_ok = [&](const p2p_gsrc* g) {
-        if (!g || !g->ptr || g->kind == 0) return true;
-        if (g->kind == 1) return g->ld % vn == 0 && g->coff % vn == 0 && ((uintptr_t)g->ptr % 16) == 0;
-        return true;    // f32 slabs are read element-wise
-    };
     const bool vec = gamma && C % 8 == 0 && draw->ld % vn == 0 && ((uintptr_t)draw->ptr % 16) == 0 &&
-                     ((uintptr_t)raw % 16) == 0 && gs_ok(g1) && gs_ok(g2);
+                     ((uintptr_t)raw % 16) == 0 && gsrc_vec_ok(g1, vn) && gsrc_vec_ok(g2, vn);
     const bool g_slabs = (g1 && g1->kind == 2) || (g2 && g2->kind == 2);      // picks the instantiation with the f32-slab loader
-    const NormRoute r = norm_bwd_route(N, H * W, C, vn, vec, g_slabs, nsplit, ws != nullptr, ws_bytes);
+    const NormRoute r = norm_bwd_route(N, H * W, C, vn, vec, g_slabs, nsplit_decode(nsplit), ws != nullptr, ws_bytes);
     if (route_out) { *route_out = norm_route_code(r); return 0; }      // the host query: nothing started
     hipStream_t st = (hipStream_t)stream;
     if (r.form == P2P_NORM_FORM_SMALL) {
@@ -1343,45 +1361,31 @@ static int norm_act_bwd_impl(int dtype, int N, int H, int W, int C, const void* 
         const long long items = (long long)N * (C / vn);
         const long long threads = items << lgG;
         const dim3 grid((unsigned)((threads + 255) / 256));
-#define NB_SMALL2(P_, S_) P2P_LAUNCH_LAST((norm_act_bwd_small<T, P_, S_>), grid, dim3(256), 0, st, H * W, W, C, lgG, items, (const T*)raw, stats, gamma, beta, act, \
-                                     alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part)
-#define NB_SMALL(P_) do { if (r.slabs) NB_SMALL2(P_, 4); else NB_SMALL2(P_, 0); } while (0)
-        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(1)); }
-        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(2)); }
-        else { P2P_DISPATCH_DTYPE(dtype, NB_SMALL(4)); }
-#undef NB_SMALL
-#undef NB_SMALL2
+        P2P_DISPATCH_DTYPE(dtype, (dispatch_ppl_slabs<4>(r.ppl, r.slabs, [&](auto P, auto S) {
+            launch256(true, norm_act_bwd_small<T, decltype(P)::value, decltype(S)::value>, grid, st, H * W, W, C, lgG, items,
+                      (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part,
+                      dbeta_part);
+        })));
         return p2p_check_launch("p2p_norm_act_bwd");
     }
     if (r.form == P2P_NORM_FORM_REG) {
-        const int rcg = r.cg;
-        const dim3 grid((unsigned)(((N + 7) / 8) * 8 * (C / rcg)));
-#define NB_REG2(P_, S_) P2P_LAUNCH_LAST((norm_act_bwd_reg<T, P_, S_>), grid, dim3(256), 0, st, N, H * W, W, C, rcg, (const T*)raw, stats, gamma, beta, act, \
-                                   alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part)
-#define NB_REG(P_) do { if (r.slabs) NB_REG2(P_, 4); else NB_REG2(P_, 0); } while (0)
-        if (r.ppl == 1) { P2P_DISPATCH_DTYPE(dtype, NB_REG(1)); }
-        else if (r.ppl == 2) { P2P_DISPATCH_DTYPE(dtype, NB_REG(2)); }
-        else if (r.ppl == 4) { P2P_DISPATCH_DTYPE(dtype, NB_REG(4)); }
-        else { P2P_DISPATCH_DTYPE(dtype, NB_REG(8)); }
-#undef NB_REG
-#undef NB_REG2
+        const dim3 grid(reg_grid(N, C, r.cg));
+        P2P_DISPATCH_DTYPE(dtype, (dispatch_ppl_slabs<8>(r.ppl, r.slabs, [&](auto P, auto S) {
+            launch256(true, norm_act_bwd_reg<T, decltype(P)::value, decltype(S)::value>, grid, st, N, H * W, W, C, r.cg, (const T*)raw,
+                      stats, gamma, beta, act, alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part);
+        })));
         return p2p_check_launch("p2p_norm_act_bwd");
     }
     if (r.form == P2P_NORM_FORM_VEC0 || r.form == P2P_NORM_FORM_VEC12) {
-        const int CG = r.cg;
-        dim3 grid(N, C / CG, r.sp);
-        if (r.form == P2P_NORM_FORM_VEC0) {
-            P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 0>), grid, dim3(256), 0, st,
-                                                      H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                                      make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
-        } else {
-            P2P_DISPATCH_DTYPE(dtype, (norm_act_bwd_vec<T, 1><<<grid, 256, 0, st>>>(
-                                          H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                          make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws)));
-            P2P_DISPATCH_DTYPE(dtype, P2P_LAUNCH_LAST((norm_act_bwd_vec<T, 2>), grid, dim3(256), 0, st,
-                                                      H, W, C, CG, (const T*)raw, stats, gamma, beta, act, alpha, mask, make_gsrc(g1),
-                                                      make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws));
-        }
+        const dim3 grid(N, C / r.cg, r.sp);
+        P2P_DISPATCH_DTYPE(dtype, ([&] {
+            auto launch = [&](auto M) {       // the partial-sum launch (MODE 1) is never an entry point's last
+                launch256(decltype(M)::value != 1, norm_act_bwd_vec<T, decltype(M)::value>, grid, st, H, W, C, r.cg, (const T*)raw, stats,
+                          gamma, beta, act, alpha, mask, make_gsrc(g1), make_gsrc(g2), make_view(draw), dgamma_part, dbeta_part, ws);
+            };
+            if (r.form == P2P_NORM_FORM_VEC0) launch(ic<0>{});
+            else { launch(ic<1>{}); launch(ic<2>{}); }
+        }()));
         return p2p_check_launch("p2p_norm_act_bwd");
     }
     int CB = pick_cb(C);
@@ -1417,8 +1421,9 @@ extern "C" int p2p_norm_act_bwd_route(int dtype, int N, int H, int W, int C, con
 // InstanceNorm over a 1x1 map (the U-Net bottleneck at 64x64 inputs).  The mean of one pixel is the pixel, so x - mean is +0
 // whatever the convolution produced: the output is act(drop(0 * gamma + beta)), d(raw) is 0, dgamma is 0 and only
 // dbeta = d(yhat) is live.  These two kernels are norm_act_fwd_small / norm_act_bwd_small at HW = 1 (one lane per (image,
-// VN-channel vector), the same expressions in the same order: bit-identical results) without the loads of x and the
-// statistics and without the store of d(raw).  (0 * gamma keeps the sign of gamma, as (x - mean) * rstd * gamma does.)
+// VN-channel vector)) without the loads of x and the statistics and without the store of d(raw): they call the same fwd_elem /
+// bwd_elem with x - mean = +0 (and rstd = 1: +0 * rstd is +0 for every rstd), so the results are bit-identical by construction.
+// (0 * gamma keeps the sign of gamma, as (x - mean) * rstd * gamma does.)
 template <typename T>
 __global__ __launch_bounds__(256) void norm_act_fwd_1x1_kernel(int C, long long items, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, int act, float alpha,
@@ -1429,15 +1434,9 @@ __global__ __launch_bounds__(256) void norm_act_fwd_1x1_kernel(int C, long long 
     const int cvn = C / VN;
     const int n = (int)(item / cvn), c = (int)(item - (long long)n * cvn) * VN;
     float keep[VN], y[VN];
-    if (mask) mask_vload8(mask + (long long)n * C + c, keep, VN);
+    if (mask) mask_vkeep<VN>(mask + (long long)n * C + c, keep);
 #pragma unroll
-    for (int k = 0; k < VN; ++k) {
-        float v = 0.f * gamma[c + k] + beta[c + k];
-        if (mask) v *= keep[k];
-        if (act == P2P_ACT_LEAKY) v = v > 0.f ? v : alpha * v;
-        else if (act == P2P_ACT_RELU) v = v > 0.f ? v : 0.f;
-        y[k] = v;
-    }
+    for (int k = 0; k < VN; ++k) y[k] = fwd_elem(0.f, 0.f, 1.f, gamma[c + k], beta[c + k], mask, mask ? keep[k] : 1.f, act, alpha);    // x - mean = +0
     vstore<T>((T*)out.ptr + out.off(n, 0, 0) + c, y);
 }
 
@@ -1454,24 +1453,13 @@ __global__ __launch_bounds__(256) void norm_act_bwd_1x1_kernel(int C, long long 
     float a1[VN], a2[VN], keep[VN];
     gsrc_vload<T, SLABS>(g1, n, c, a1);
     gsrc_vload<T, SLABS>(g2, n, c, a2);
-    if (mask) mask_vload8(mask + (long long)n * C + c, keep, VN);
+    if (mask) mask_vkeep<VN>(mask + (long long)n * C + c, keep);
 #pragma unroll
     for (int k = 0; k < VN; ++k) {
-        float a = 0.f * gamma[c + k] + beta[c + k];
-        const float kp = mask ? keep[k] : 1.f;
-        a *= kp;
-        float slope = 1.f;
-        if (act == P2P_ACT_LEAKY) slope = a > 0.f ? 1.f : alpha;
-        else if (act == P2P_ACT_RELU) slope = a > 0.f ? 1.f : 0.f;
-        const float d = (a1[k] + a2[k]) * slope * kp;
+        const float d = bwd_elem(true, 0.f, gamma[c + k], beta[c + k], mask ? keep[k] : 1.f, a1[k] + a2[k], act, alpha);    // xhat = +0
         dbeta_part[(long long)n * C + c + k] = 0.f + d;     // (the sum over one pixel starts from +0)
         dgamma_part[(long long)n * C + c + k] = 0.f;
     }
-}
-
-static bool gsrc_vec_ok(const p2p_gsrc* g, int vn) {
-    if (!g || !g->ptr || g->kind != 1) return true;     // f32 slabs are read element-wise unless they are aligned
-    return g->ld % vn == 0 && g->coff % vn == 0 && ((uintptr_t)g->ptr % 16) == 0;
 }
 
 extern "C" int p2p_norm_act_fwd_1x1(int dtype, int N, int C, const float* gamma, const float* beta, int act, float alpha,
@@ -1500,11 +1488,10 @@ extern "C" int p2p_norm_act_bwd_1x1(int dtype, int N, int C, const float* gamma,
     const long long items = (long long)N * (C / vn);
     const dim3 grid((unsigned)((items + 255) / 256));
     hipStream_t st = (hipStream_t)stream;
-#define NB_1X1(S_) norm_act_bwd_1x1_kernel<T, S_><<<grid, 256, 0, st>>>(C, items, gamma, beta, act, alpha, mask, make_gsrc(g1), make_gsrc(g2), \
-                                                                       dgamma_part, dbeta_part)
-    if (g_slabs) { P2P_DISPATCH_DTYPE(dtype, NB_1X1(4)); }
-    else { P2P_DISPATCH_DTYPE(dtype, NB_1X1(0)); }
-#undef NB_1X1
+    P2P_DISPATCH_DTYPE(dtype, (dispatch_slabs(g_slabs, [&](auto S) {
+        norm_act_bwd_1x1_kernel<T, decltype(S)::value><<<grid, 256, 0, st>>>(C, items, gamma, beta, act, alpha, mask, make_gsrc(g1),
+                                                                             make_gsrc(g2), dgamma_part, dbeta_part);
+    })));
     return p2p_check_launch("p2p_norm_act_bwd_1x1");
 }
 
