@@ -534,6 +534,29 @@ int p2p_palette_project_fwd(int N, int H, int W, const float* img, const int* pa
 int p2p_palette_project_bwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau,
                             const float* g, float* dimg, void* stream);
 
+/* Palette lookup: the RGBA image of the indexed model's probabilities.  probs, dprobs: dense f32 [N][H][W][K];
+ * palette: int32 [N][K][4], RGBA rows in 0..255; out, g: dense f32 [N][H][W][4]; every pointer 16-byte aligned; any H, W >= 1
+ * (H * W <= 2^30, N <= 65535); K must be 256, as for p2p_softmax_bwd; hard and blacken are 0 or 1.  Anything else returns a negative
+ * code before any launch.  With t_k = palette[n][k] / 127.5f - 1.0f per channel (the two f32 operations of p2p_palette_snap's
+ * image_out) and, with blacken = 1, the RGB of a slot whose alpha is 0 set to 0 first (t_k = (-1, -1, -1, -1):
+ * dataset_utils.blacken_transparent_pixels applied to the palette):
+ *   hard = 0:  out_p = sum_k probs_pk t_k.  Linear: no offset, nothing assumes that a row sums to 1; a one-hot row (an exact 1.0f and
+ *              zeros) returns the bits of t_k.  One wave reduces one pixel: four FMAs per channel in every lane (slots 4 lane ..
+ *              4 lane + 3, ascending), then an xor butterfly (offsets 32, 16, .., 1) over the 64 lanes.  The same lanes in the same
+ *              order for every pixel; no atomics, no workspace: a pixel's bits depend on neither N, nor its image's place in the
+ *              batch, nor a second launch.
+ *   hard = 1:  out_p = t_argmax_k probs_pk, ties to the lowest k (the rule of p2p_argmax_lastdim): bit-equal to a gather.
+ * Every pixel of out is written. */
+int p2p_palette_lookup_fwd(int N, int H, int W, int K, const float* probs, const int* palette, int hard, int blacken,
+                           float* out, void* stream);
+/* Its VJP with respect to probs for an upstream gradient g -- the same for both forwards (for hard = 1 the straight-through
+ * surrogate); the palette is not differentiable and probs is not needed:
+ *   dprobs_pk = ((g_p0 t_k0 + g_p1 t_k1) + g_p2 t_k2) + g_p3 t_k3,
+ * every product and every sum rounded to f32 on its own (no FMA contraction), so a float32 restatement matches bit for bit.  Every
+ * element of dprobs is written: a 1 KB-per-pixel write stream. */
+int p2p_palette_lookup_bwd(int N, int H, int W, int K, const float* g, const int* palette, int blacken,
+                           float* dprobs, void* stream);
+
 /* ---- differentiable augmentation (build-added, DESIGN.md "differentiable augmentation") --------------------------- */
 /* DiffAugment (Zhao et al., NeurIPS 2020) of dense f32 RGBA images [N][H][W][4], 16-byte aligned, any H, W >= 1 (H * W <= 2^28,
  * N <= 65535).  color: f32 [N][3] = brightness offset b, saturation factor s, contrast factor k; geometry: int32 [N][4] = ty, tx,

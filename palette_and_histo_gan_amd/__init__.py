@@ -6,4 +6,12 @@ include/p2pgan.h.  Importing the package does not need a GPU; constructing a mod
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "Pix2PixIndexedColourModel"]
+
+
+def __getattr__(name):
+    """the build-added model classes by name, imported on first use (pix2pix_model pulls in torch and the engine)"""
+    if name == "Pix2PixIndexedColourModel":
+        from .pix2pix_model import Pix2PixIndexedColourModel
+        return Pix2PixIndexedColourModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -97,6 +97,8 @@ SIGNATURES = {
     "p2p_palette_snap": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "p2p_palette_project_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _vp],
     "p2p_palette_project_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
+    "p2p_palette_lookup_fwd": [_i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp],
+    "p2p_palette_lookup_bwd": [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
     "p2p_diffaug_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "p2p_diffaug_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "p2p_softmax_cce_argmax": [_i, _i, _i, _i, _i, _TP, _TP, _TP, _f, _f, _TP, _vp, _vp, _vp, _vp],

@@ -73,6 +73,7 @@ constexpr Entry TABLE[] = {
     P2P_E(p2p_palette_snap) P2P_E(p2p_diffaug_fwd) P2P_E(p2p_diffaug_bwd)
     P2P_E(p2p_palette_project_fwd) P2P_E(p2p_palette_project_bwd)
     P2P_E(p2p_soft_palette_tv_bwd) P2P_E(p2p_palette_loss) P2P_E(p2p_finish_losses2)
+    P2P_E(p2p_palette_lookup_fwd) P2P_E(p2p_palette_lookup_bwd)
 };
 #undef P2P_E
 constexpr int NFN = (int)(sizeof(TABLE) / sizeof(TABLE[0]));

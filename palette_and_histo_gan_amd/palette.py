@@ -11,7 +11,10 @@ palette colour in exact integer arithmetic, per-slot counts, off-palette pixels)
 (Pix2PixModel.generate(snap=)) and evaluation (`palette_metrics`, S2SModel.report_palette).  `project_to_palette` stands between the two: it replaces every pixel by a
 palette colour -- the soft expected colour or the snap itself -- and IS differentiable (p2p_palette_project_fwd / _bwd: the exact
 Jacobian of the soft projection, or the straight-through identity), so a tape step can show the discriminator what survives the snap
-(Pix2PixPaletteSnapModel).  All kernels launch on the current stream; there is no CPU path.
+(Pix2PixPaletteSnapModel).  `palette_lookup` serves the palette-index model instead: it maps (B, H, W, 256)
+probabilities over a palette's slots to the RGBA image they stand for (p2p_palette_lookup_fwd / _bwd: the expected colour, or the
+argmax's colour with the straight-through gradient), so image-space losses reach the indexed generator (Pix2PixIndexedColourModel;
+DESIGN.md 6g).  All kernels launch on the current stream; there is no CPU path.
 
 The default temperature 1e-3 makes a pixel that sits on a palette colour count for that slot alone (two colours one 8-bit step apart
 in one channel are 1.5e-5 apart in d, a weight ratio of 0.985; a pixel half-way between two clearly different colours is shared).
@@ -218,6 +221,61 @@ def project_to_palette(image_batch, palette, sizes=None, temperature=5e-2, hard=
     pal, sz = _palette_args(pal, sizes, B, dev)
     with torch.cuda.device(dev):
         return PaletteProjection.apply(img, pal, sz, temperature, bool(hard), gradient == "soft")
+
+
+class PaletteLookup(torch.autograd.Function):
+    """probs: dense f32 (B, H, W, 256) device tensor; palette int32 (B, 256, 4) dense on its device -> RGBA image (B, H, W, 4).
+    Backward: with respect to probs only, single backward (p2p_palette_lookup_bwd: the soft map's VJP for both forwards); only the
+    palette is saved."""
+
+    @staticmethod
+    def forward(ctx, probs, palette, hard, blacken):
+        B, H, W, K = (int(x) for x in probs.shape)
+        out = torch.empty((B, H, W, 4), dtype=torch.float32, device=probs.device)
+        L.call("p2p_palette_lookup_fwd", B, H, W, K, _p(probs), _p(palette), int(hard), int(blacken), _p(out), _stream(probs.device))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(palette)
+            ctx.blacken = blacken
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        palette, = ctx.saved_tensors
+        B, H, W, _ = (int(x) for x in grad_out.shape)
+        K = int(palette.shape[1])
+        dev = palette.device
+        g = grad_out.to(torch.float32).contiguous()
+        dprobs = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.call("p2p_palette_lookup_bwd", B, H, W, K, _p(g), _p(palette), int(ctx.blacken), _p(dprobs), _stream(dev))
+        return dprobs, None, None, None
+
+
+def palette_lookup(probs, palette, hard=False, blacken=False, device=None):
+    """The RGBA image (B, H, W, 4), f32 in [-1, 1], of per-pixel probabilities (B, H, W, 256) over the slots of per-image palettes
+    (B, 256, 4) of 0..255 RGBA rows -- what Pix2PixIndexedModel's generator puts out, seen as an image.  With
+    t_k = palette_k / 127.5 - 1 (the dataset's normalisation):
+        hard=False   y_p = sum_k probs_pk t_k: the expected colour; linear, a one-hot row returns t_k bit for bit
+        hard=True    y_p = t_argmax_k probs_pk (ties: the lowest k): io_utils.indexed_to_rgba of the argmax, normalised
+        blacken      the RGB of a slot whose alpha is 0 counts as 0, as dataset_utils.blacken_transparent_pixels leaves an image
+    Differentiable with respect to `probs` only (the gradient has its shape, dtype and device): dL/dprobs_pk = <dL/dy_p, t_k> for both
+    forwards -- for hard=True the straight-through surrogate, the argmax's own gradient being 0 almost everywhere.  Integer indices
+    (B, H, W, 1) are not probabilities: io_utils.indexed_to_rgba maps those."""
+    L.lib()          # fail loudly if the HIP library is missing: there is no CPU path
+    dev = _device_of(probs, device)
+    p = torch.as_tensor(probs)
+    if p.dim() != 4 or p.shape[3] != MAX_PALETTE_SIZE or p.numel() == 0:
+        raise ValueError(f"expected non-empty (B, H, W, {MAX_PALETTE_SIZE}) probabilities, got {tuple(p.shape)}"
+                         + (": integer indices are mapped by io_utils.indexed_to_rgba" if p.dim() == 4 and p.shape[3] == 1 else ""))
+    B = int(p.shape[0])
+    pal = torch.as_tensor(palette)
+    if tuple(pal.shape) != (B, MAX_PALETTE_SIZE, 4):
+        raise ValueError(f"expected a ({B}, {MAX_PALETTE_SIZE}, 4) palette for a batch of {B}, got {tuple(pal.shape)}")
+    p = p.to(device=dev, dtype=torch.float32).contiguous()          # stays on the autograd graph
+    pal = pal.detach().to(device=dev, dtype=torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        return PaletteLookup.apply(p, pal, bool(hard), bool(blacken))
 
 
 PaletteSnap = collections.namedtuple("PaletteSnap", "index image distance counts off_palette distance_sum")

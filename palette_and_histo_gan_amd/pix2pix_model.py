@@ -7,6 +7,7 @@
     Pix2PixPaletteModel(..., lambda_l1, lambda_palette, lambda_conformance=0.0, temperature=1e-3)      -- build-added
     Pix2PixDiffAugmentModel(..., lambda_l1, policy="color,translation,cutout")                         -- build-added
     Pix2PixPaletteSnapModel(..., lambda_l1, hard=True, gradient="identity", temperature=5e-2)          -- build-added
+    Pix2PixIndexedColourModel(..., lambda_segmentation=0.5, lambda_colour=100.0, lambda_histogram=0.0, hard=False, blacken=True)  -- build-added
 
 The constructor follows the reference's (pix2pix_model.py:12-36): create_generator() / create_discriminator() with the
 reference's builder signatures, `loss_object`, two Adam(0.0002, beta_1=0.5) optimizers, `checkpoint`,
@@ -625,3 +626,71 @@ class Pix2PixIndexedModel(Pix2PixModel):
         fake = self.generate(batch).to(torch.float32)
         target = torch.as_tensor(batch[1], dtype=torch.float32).to(fake.device)
         return (target - fake).abs().mean()
+
+
+class Pix2PixIndexedColourModel(Pix2PixIndexedModel):
+    """Build-added (no counterpart in the reference): the palette-index model with losses that know what a palette slot
+    LOOKS like.  The parent's generator learns from lambda_segmentation * CCE alone, to which every wrong slot costs the same -- one
+    shade off or the hot-pink filler that pads the palette.  Here the probabilities are mapped through the batch's palette to an RGBA
+    image (palette.palette_lookup: the expected colour, or with `hard` the argmax's colour with the straight-through gradient;
+    `blacken` treats transparent slots as dataset_utils.blacken_transparent_pixels treats transparent pixels) and generator_loss adds
+        lambda_colour * mean |real_rgba - fake_rgba|
+        + lambda_histogram * hellinger_loss(calculate_rgbuv_histogram(real_rgba), calculate_rgbuv_histogram(fake_rgba)),
+    real_rgba being the palette gather of the real indices.  At lambda_histogram == 0 the histogram term is not computed (no launch).
+    train_step keeps the batch's palette on the device for the hook and otherwise is the parent's hooked step
+    (differentiable_loss_hooks: engine.train_step_indexed_hooked, one GPU, not replayed); it returns and logs the two terms behind the
+    parent's four (generator/colour_l1_loss, generator/histogram_loss).
+    The class does NOT change what the discriminator sees: it still judges argmax indices, and the argmax still blocks every gradient
+    from the discriminator to the generator.  The colour terms reach the generator through the probabilities only."""
+
+    differentiable_loss_hooks = True
+
+    def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_segmentation=0.5, lambda_colour=100.0,
+                 lambda_histogram=0.0, hard=False, blacken=True, **kw):
+        for name, value in (("lambda_colour", lambda_colour), ("lambda_histogram", lambda_histogram)):
+            if not float(value) >= 0.0:
+                raise ValueError(f"{name} must not be negative, got {value}")
+        super().__init__(train_ds, test_ds, model_name, architecture_name, lambda_segmentation, **kw)
+        self.lambda_colour, self.lambda_histogram = float(lambda_colour), float(lambda_histogram)
+        self.hard, self.blacken = bool(hard), bool(blacken)
+        self._step_palette = None
+        self._colour_terms = None
+
+    def generator_loss(self, fake_predicted, fake_image, real_image, palette=None):
+        """fake_image = probabilities, real_image = one-hot, as the parent's; `palette` (B, 256, 4): the batch's palette for a
+        standalone evaluation (train_step supplies its own batch's)."""
+        palette = self._step_palette if palette is None else palette
+        if palette is None:
+            raise ValueError("Pix2PixIndexedColourModel.generator_loss needs the batch's palette: pass palette=, or call train_step")
+        total_loss, adversarial_loss, l1_loss, segmentation_loss = super().generator_loss(fake_predicted, fake_image, real_image)
+        dev = self.engine.device
+        fake_rgba = _palette.palette_lookup(fake_image, palette, self.hard, self.blacken, device=dev)
+        with torch.no_grad():       # a one-hot row's argmax is its index: the palette gather of the real indices, bit for bit
+            real_rgba = _palette.palette_lookup(real_image, palette, True, self.blacken, device=dev)
+        colour_loss = (real_rgba - fake_rgba).abs().mean()
+        total_loss = total_loss + self.lambda_colour * colour_loss
+        if self.lambda_histogram != 0.0:
+            real_histogram = _histogram.calculate_rgbuv_histogram(real_rgba, device=dev)
+            fake_histogram = _histogram.calculate_rgbuv_histogram(fake_rgba, device=dev)
+            histogram_loss = _histogram.hellinger_loss(real_histogram, fake_histogram)
+            total_loss = total_loss + self.lambda_histogram * histogram_loss
+        else:
+            histogram_loss = torch.zeros((), dtype=torch.float32, device=colour_loss.device)
+        self._colour_terms = (colour_loss.detach(), histogram_loss.detach())
+        return total_loss, adversarial_loss, l1_loss, segmentation_loss, colour_loss, histogram_loss
+
+    def train_step(self, batch, step, update_steps):
+        self._check_hooks()          # data parallelism is refused before anything is uploaded
+        self._step_palette = torch.as_tensor(batch[2]).to(device=self.engine.device, dtype=torch.int32)
+        self._colour_terms = None
+        try:
+            g_loss, d_loss = super().train_step(batch, step, update_steps)
+        finally:
+            self._step_palette = None
+        return g_loss + self._colour_terms, d_loss
+
+    def log_generator_loss(self, g_loss, step):
+        super().log_generator_loss(g_loss[:4], step)
+        colour_loss, histogram_loss = self._colour_terms
+        self.summary_writer.scalar("generator/colour_l1_loss", colour_loss, step)
+        self.summary_writer.scalar("generator/histogram_loss", histogram_loss, step)
