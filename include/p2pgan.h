@@ -652,6 +652,83 @@ int p2p_adam_ema_flat_dev_excl(float* p, const float* g, float* m, float* v, flo
                                int warmup, void* stream);
 int p2p_ema_flat(float* e, const float* p, long long n, const int* t_dev, float decay, int warmup, void* stream);
 int p2p_counter_add(long long* counter_dev, long long inc, void* stream);
+
+/* ---- optimizer options: learning-rate schedules, gradient clipping ------------------------------- */
+
+/* A learning-rate schedule, evaluated on the DEVICE from the step counter: lr(step) in f64 with the formulas of Keras 2.9's
+ * tf.keras.optimizers.schedules (names below), step = the iteration count BEFORE the increment (Keras evaluates a schedule at
+ * `iterations`, then increments).  A HOST struct, read when the call is issued (it travels to the kernel by value).
+ *   P2P_LR_CONSTANT     lr = initial
+ *   P2P_LR_EXPONENTIAL  ExponentialDecay: p = step / decay_steps; flag (staircase): p = floor(p); lr = initial * rate^p
+ *   P2P_LR_PIECEWISE    PiecewiseConstantDecay: values[0] if step <= bounds[0]; values[i] if bounds[i-1] < step <= bounds[i];
+ *                       values[nbounds] if step > bounds[nbounds-1]        (nbounds <= 8)
+ *   P2P_LR_POLYNOMIAL   PolynomialDecay: flag (cycle): d = decay_steps * (step == 0 ? 1 : ceil(step / decay_steps)), s = step;
+ *                       else d = decay_steps, s = min(step, decay_steps);  lr = (initial - end) * (1 - s / d)^power + end
+ *   P2P_LR_COSINE       CosineDecay: s = min(step, decay_steps); lr = initial * ((1 - rate) * 0.5 * (1 + cos(pi * s / decay_steps)) + rate)
+ *                       (rate = alpha)
+ *   P2P_LR_LINEAR       build-added LinearDecay (the pix2pix recipe): initial while step < hold_steps, `end` from
+ *                       step >= hold_steps + decay_steps on, initial + (end - initial) * (step - hold_steps) / decay_steps between
+ * warmup_steps > 0 multiplies any kind by (step + 1) / warmup_steps while step < warmup_steps. */
+enum { P2P_LR_CONSTANT = 0, P2P_LR_EXPONENTIAL = 1, P2P_LR_PIECEWISE = 2, P2P_LR_POLYNOMIAL = 3, P2P_LR_COSINE = 4,
+       P2P_LR_LINEAR = 5 };
+typedef struct p2p_lr_schedule {
+    int kind, flag, nbounds, pad_;
+    double initial, decay_steps, rate, end, power, hold_steps, warmup_steps;
+    double bounds[8], values[9];
+} p2p_lr_schedule;
+/* p2p_adam_tick with the rate taken from a schedule: t_dev[0] += 1 (-> t), lr = sched(t - 1) in f64,
+ * lr_t_dev[0] = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t)).  P2P_LR_CONSTANT without warm-up, initial = (double)(float)lr:
+ * the bits of p2p_adam_tick.  The device's f64 pow and cos are not correctly rounded: other kinds may differ from a host
+ * evaluation by 1 ulp of the f32 result. */
+int p2p_adam_tick_sched(int* t_dev, float* lr_t_dev, const p2p_lr_schedule* sched, float beta1, float beta2, void* stream);
+
+/* Global L2 norm of a flat f32 gradient and the scale tf.clip_by_global_norm applies, in a FIXED summation order that depends
+ * on n alone (not on the batch, the resident grid or the stream; no atomics), every operation a correctly rounded f32 one
+ * without contraction (sq = g * g rounded, then acc + sq), so a NumPy float32 restatement reproduces the bits
+ * (tests/optimizer_oracle.py):
+ *   p2p_sumsq_partials   V = n / 4 whole 16-byte vectors, NB = min(max(ceil(V / 256), 1), P2P_SUMSQ_MAX_PARTS) workgroups of
+ *       256 threads.  Thread q = 256 * b + tid starts with acc = 0 and walks the vectors j = q, q + 256 * NB, ... in rising
+ *       order, within a vector the components 0, 1, 2, 3 in order: acc = acc + g * g.  An element inside the hole
+ *       [ex_lo, ex_hi) counts as 0 (a vector wholly inside is not read).  Thread 0 of workgroup 0 then adds the n % 4 tail
+ *       elements in rising order.  Wave tree: for off = 32, 16, 8, 4, 2, 1: acc[l] = acc[l] + acc[l + off] (lane 0 holds the
+ *       wave's sum).  Workgroup: ((w0 + w1) + w2) + w3 over its four waves -> partials[b].  *nparts_out = NB (HOST int, written
+ *       when the call is issued).  partials: room for P2P_SUMSQ_MAX_PARTS floats.
+ *   p2p_clip_scale       the partials of nbuf (<= 8) buffers, concatenated in argument order into one list c[0 .. M): one wave;
+ *       lane l: acc = 0, then acc = acc + c[i] for i = l, l + 64, ... rising; the same wave tree; norm = sqrt(lane 0's sum);
+ *       scale = norm > clipnorm ? clipnorm / norm (one correctly rounded division) : 1.0f -- EXACTLY 1 at and below the
+ *       threshold, where TF's clip_norm * min(1 / norm, 1 / clip_norm) may be 1 ulp off 1; a non-finite norm gives a NaN
+ *       scale, as tf.clip_by_global_norm does.  scale_dev[0] = scale, norm_dev[0] = norm (kept for logging without a sync).
+ *       `partials` and `nparts` are HOST arrays (of device pointers / of counts), read when the call is issued. */
+enum { P2P_SUMSQ_MAX_PARTS = 1024, P2P_CLIP_MAX_BUFS = 8 };
+int p2p_sumsq_partials(const float* g, long long n, long long ex_lo, long long ex_hi, float* partials, int* nparts_out,
+                       void* stream);
+int p2p_clip_scale(const float* const* partials, const int* nparts, int nbuf, float clipnorm, float* scale_dev, float* norm_dev,
+                   void* stream);
+
+/* One Adam launch over a flat buffer with every option as a field: what p2p_adam_flat_dev, _excl, p2p_adam_ema_flat_dev and
+ * _excl do (e null: no moving average; ex_lo == ex_hi: no hole), plus
+ *   gscale_dev   device scalar the gradient is multiplied by (p2p_clip_scale's; null: 1)
+ *   clipvalue    hyper->clipvalue > 0: g = fminf(fmaxf(g, -c), c) before everything else (<= 0: off)
+ * Both are HOST structs read when the call is issued; `hyper` is shared by every launch of one optimizer.  The element goes
+ * through the same update as the four entry points: with both options off the results are theirs bit for bit. */
+typedef struct p2p_adam_hyper {
+    float beta1, beta2, eps, clipvalue, ema_decay;
+} p2p_adam_hyper;
+typedef struct p2p_adam_args {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* e;
+    long long n, ex_lo, ex_hi;
+    const float* lr_t_dev;
+    const float* gscale_dev;
+    const int* t_dev;
+    const p2p_adam_hyper* hyper;
+    int ema_warmup, pad_;
+} p2p_adam_args;
+int p2p_adam_step(const p2p_adam_args* a, void* stream);
+
 /* f32 gradient sum of a GradientTape (tape.py): a network's weight gradients over several calls, the two terms of a generator
  * call's d(source).  dst = src when `first` is set (the first contribution), dst += src otherwise; n floats, 16-byte aligned,
  * no atomics (bit-reproducible). */

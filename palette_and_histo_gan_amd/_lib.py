@@ -64,6 +64,10 @@ SIGNATURES = {
     "p2p_adam_ema_flat_dev_excl": [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _f, _f, _f, _f, _vp, _f, _i, _vp],
     "p2p_ema_flat": [_vp, _vp, _ll, _vp, _f, _i, _vp],
     "p2p_counter_add": [_vp, _ll, _vp],
+    "p2p_adam_tick_sched": [_vp, _vp, _vp, _f, _f, _vp],
+    "p2p_sumsq_partials": [_vp, _ll, _ll, _ll, _vp, _vp, _vp],
+    "p2p_clip_scale": [_vp, _vp, _i, _f, _vp, _vp, _vp],
+    "p2p_adam_step": [_vp, _vp],
     "p2p_grad_accumulate": [_vp, _vp, _ll, _i, _vp],
     "p2p_dropout_mask_dev": [_vp, _ll, _ll, _vp, _ll, _ll, _vp],
     "p2p_weight_prep": [_i, _vp, _i, _i, _vp, _vp, _vp],
@@ -163,6 +167,31 @@ class PrepTask(C.Structure):
                 ("Cg", C.c_int), ("Cd", C.c_int), ("wn_rows", C.c_int), ("wn_cols", C.c_int),
                 ("wt_rows", C.c_int), ("wt_cols", C.c_int), ("tiles_g", C.c_int), ("tiles_d", C.c_int),
                 ("first_block", C.c_longlong)]
+
+
+class LrSchedule(C.Structure):
+    """include/p2pgan.h p2p_lr_schedule"""
+    CONSTANT, EXPONENTIAL, PIECEWISE, POLYNOMIAL, COSINE, LINEAR = range(6)
+    _fields_ = [("kind", C.c_int), ("flag", C.c_int), ("nbounds", C.c_int), ("pad_", C.c_int),
+                ("initial", C.c_double), ("decay_steps", C.c_double), ("rate", C.c_double), ("end", C.c_double),
+                ("power", C.c_double), ("hold_steps", C.c_double), ("warmup_steps", C.c_double),
+                ("bounds", C.c_double * 8), ("values", C.c_double * 9)]
+
+
+class AdamHyper(C.Structure):
+    """include/p2pgan.h p2p_adam_hyper"""
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("clipvalue", C.c_float), ("ema_decay", C.c_float)]
+
+
+class AdamArgs(C.Structure):
+    """include/p2pgan.h p2p_adam_args"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("e", C.c_void_p),
+                ("n", C.c_longlong), ("ex_lo", C.c_longlong), ("ex_hi", C.c_longlong),
+                ("lr_t_dev", C.c_void_p), ("gscale_dev", C.c_void_p), ("t_dev", C.c_void_p), ("hyper", C.POINTER(AdamHyper)),
+                ("ema_warmup", C.c_int), ("pad_", C.c_int)]
+
+
+SUMSQ_MAX_PARTS = 1024      # include/p2pgan.h P2P_SUMSQ_MAX_PARTS
 
 _lib = None
 

@@ -268,6 +268,253 @@ extern "C" int p2p_ema_flat(float* e, const float* p, long long n, const int* t_
     return p2p_check_launch("p2p_ema_flat");
 }
 
+// ---- optimizer options --------------------------------------------------------------------------------
+// Learning-rate schedules of Keras 2.9 (tf.keras.optimizers.schedules: ExponentialDecay, PiecewiseConstantDecay, PolynomialDecay,
+// CosineDecay) and the build-added LinearDecay, restated in f64 and evaluated at `step` = the iteration count before the increment
+// (OptimizerV2._decayed_lr evaluates the schedule at `iterations`; apply_gradients increments afterwards).  Definitions:
+// include/p2pgan.h p2p_lr_schedule; host restatement: palette_and_histo_gan_amd/schedules.py.
+__device__ __forceinline__ double lr_schedule(const p2p_lr_schedule& s, double step) {
+    double lr = s.initial;
+    switch (s.kind) {
+    case P2P_LR_EXPONENTIAL: {      // ExponentialDecay.__call__: initial * decay_rate ^ (step / decay_steps), floor under staircase
+        double p = step / s.decay_steps;
+        if (s.flag) p = floor(p);
+        lr = s.initial * pow(s.rate, p);
+        break;
+    }
+    case P2P_LR_PIECEWISE: {        // PiecewiseConstantDecay.__call__: the boundaries are inclusive on the right
+        int i = 0;
+        while (i < s.nbounds && step > s.bounds[i]) ++i;
+        lr = s.values[i];
+        break;
+    }
+    case P2P_LR_POLYNOMIAL: {       // PolynomialDecay.__call__
+        double d = s.decay_steps, g = step;
+        if (s.flag) d = s.decay_steps * (step == 0.0 ? 1.0 : ceil(step / s.decay_steps));
+        else g = fmin(step, s.decay_steps);
+        lr = (s.initial - s.end) * pow(1.0 - g / d, s.power) + s.end;
+        break;
+    }
+    case P2P_LR_COSINE: {           // CosineDecay.__call__ (alpha = rate)
+        const double c = 0.5 * (1.0 + cos(3.14159265358979323846 * (fmin(step, s.decay_steps) / s.decay_steps)));
+        lr = s.initial * ((1.0 - s.rate) * c + s.rate);
+        break;
+    }
+    case P2P_LR_LINEAR:             // LinearDecay: constant, then linear, then `end`
+        if (step >= s.hold_steps + s.decay_steps) lr = s.end;
+        else if (step >= s.hold_steps) lr = s.initial + (s.end - s.initial) * ((step - s.hold_steps) / s.decay_steps);
+        break;
+    default: break;
+    }
+    if (s.warmup_steps > 0.0 && step < s.warmup_steps) lr = lr * ((step + 1.0) / s.warmup_steps);
+    return lr;
+}
+
+__global__ void adam_tick_sched_kernel(int* __restrict__ t, float* __restrict__ lr_t, p2p_lr_schedule s, float b1, float b2) {
+    int tt = t[0] + 1;
+    t[0] = tt;
+    const double lr = lr_schedule(s, (double)(tt - 1));
+    lr_t[0] = (float)(lr * sqrt(1.0 - pow((double)b2, (double)tt)) / (1.0 - pow((double)b1, (double)tt)));
+}
+
+extern "C" int p2p_adam_tick_sched(int* t_dev, float* lr_t_dev, const p2p_lr_schedule* sched, float beta1, float beta2,
+                                   void* stream) {
+    P2P_REQUIRE(t_dev && lr_t_dev && sched, "p2p_adam_tick_sched: null pointer");
+    P2P_REQUIRE(sched->kind >= P2P_LR_CONSTANT && sched->kind <= P2P_LR_LINEAR, "p2p_adam_tick_sched: unknown schedule kind %d",
+                sched->kind);
+    P2P_REQUIRE(sched->kind != P2P_LR_PIECEWISE || (sched->nbounds >= 1 && sched->nbounds <= 8),
+                "p2p_adam_tick_sched: a piecewise schedule holds 1..8 boundaries, got %d", sched->nbounds);
+    P2P_REQUIRE(sched->kind == P2P_LR_CONSTANT || sched->kind == P2P_LR_PIECEWISE || sched->decay_steps > 0.0,
+                "p2p_adam_tick_sched: decay_steps must be positive");
+    adam_tick_sched_kernel<<<1, 1, 0, (hipStream_t)stream>>>(t_dev, lr_t_dev, *sched, beta1, beta2);
+    return p2p_check_launch("p2p_adam_tick_sched");
+}
+
+// Global gradient norm in a fixed order (include/p2pgan.h p2p_sumsq_partials: lane, vector component, wave tree, block partial;
+// p2p_clip_scale: lane-strided serial sums of the partials, wave tree).  Every add and multiply is a rounded f32 operation.
+__device__ __forceinline__ float wave_tree_sum(float acc) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_down(acc, off, 64);
+    return acc;         // lane 0: the tree's root; the other lanes hold sums nobody reads
+}
+
+__global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __restrict__ g, long long n, long long ex_lo, long long ex_hi,
+                                                             float* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ float wsum[4];
+    const long long nvec = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    float acc = 0.f;
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < nvec; j += stride) {
+        const long long i = j * 4;
+        if (i >= ex_lo && i + 4 <= ex_hi) continue;             // wholly inside the hole: four zeros, acc unchanged
+        const f32x4 gi = *(const f32x4*)(g + i);
+        const bool whole = i + 4 <= ex_lo || i >= ex_hi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gk = (whole || i + k < ex_lo || i + k >= ex_hi) ? gi[k] : 0.f;
+            const float sq = gk * gk;
+            acc = acc + sq;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = nvec * 4; j < n; ++j) {
+            const float gk = (j < ex_lo || j >= ex_hi) ? g[j] : 0.f;
+            const float sq = gk * gk;
+            acc = acc + sq;
+        }
+    acc = wave_tree_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+static inline int sumsq_blocks(long long n) {
+    long long nb = (n / 4 + 255) / 256;
+    if (nb < 1) nb = 1;
+    if (nb > P2P_SUMSQ_MAX_PARTS) nb = P2P_SUMSQ_MAX_PARTS;
+    return (int)nb;
+}
+
+extern "C" int p2p_sumsq_partials(const float* g, long long n, long long ex_lo, long long ex_hi, float* partials, int* nparts_out,
+                                  void* stream) {
+    P2P_REQUIRE(g && partials && nparts_out && n > 0, "p2p_sumsq_partials: bad args");
+    P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_sumsq_partials: the excluded range must lie inside [0, n)");
+    P2P_REQUIRE(((uintptr_t)g % 16) == 0, "p2p_sumsq_partials: the gradient must be 16-byte aligned");
+    const int nb = sumsq_blocks(n);
+    sumsq_partials_kernel<<<dim3((unsigned)nb), 256, 0, (hipStream_t)stream>>>(g, n, ex_lo, ex_hi, partials);
+    *nparts_out = nb;
+    return p2p_check_launch("p2p_sumsq_partials");
+}
+
+struct ClipBufs { const float* p[P2P_CLIP_MAX_BUFS]; int n[P2P_CLIP_MAX_BUFS]; int nbuf; };
+
+__global__ void __launch_bounds__(64) clip_scale_kernel(ClipBufs b, float clipnorm, float* __restrict__ scale, float* __restrict__ norm_out) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    int base = 0;           // index of the buffer's first partial in the concatenated list
+    for (int k = 0; k < b.nbuf; ++k) {
+        // lane l takes the list entries l, l + 64, ...: inside buffer k those are its entries i with (base + i) % 64 == l
+        for (int i = ((int)threadIdx.x - base % 64 + 64) % 64; i < b.n[k]; i += 64) acc = acc + b.p[k][i];
+        base += b.n[k];
+    }
+    acc = wave_tree_sum(acc);
+    if (threadIdx.x == 0) {
+        const float norm = sqrtf(acc);              // correctly rounded, as in adam_update (the _rn intrinsic is the native, approximate one)
+        float s = 1.0f;
+        if (!isfinite(norm)) s = __builtin_nanf("");                    // tf.clip_by_global_norm: non-finite norm -> NaN everywhere
+        else if (norm > clipnorm) s = __fdiv_rn(clipnorm, norm);
+        scale[0] = s;
+        norm_out[0] = norm;
+    }
+}
+
+extern "C" int p2p_clip_scale(const float* const* partials, const int* nparts, int nbuf, float clipnorm, float* scale_dev,
+                              float* norm_dev, void* stream) {
+    P2P_REQUIRE(partials && nparts && scale_dev && norm_dev && nbuf >= 1 && nbuf <= P2P_CLIP_MAX_BUFS, "p2p_clip_scale: bad args");
+    P2P_REQUIRE(clipnorm > 0.f, "p2p_clip_scale: the threshold must be positive");
+    ClipBufs b;
+    b.nbuf = nbuf;
+    for (int k = 0; k < P2P_CLIP_MAX_BUFS; ++k) {
+        b.p[k] = k < nbuf ? partials[k] : nullptr;
+        b.n[k] = k < nbuf ? nparts[k] : 0;
+        P2P_REQUIRE(k >= nbuf || (b.p[k] && b.n[k] >= 1 && b.n[k] <= P2P_SUMSQ_MAX_PARTS), "p2p_clip_scale: buffer %d: bad partials", k);
+    }
+    clip_scale_kernel<<<1, 64, 0, (hipStream_t)stream>>>(b, clipnorm, scale_dev, norm_dev);
+    return p2p_check_launch("p2p_clip_scale");
+}
+
+// p2p_adam_step: adam_flat_dev_excl_kernel's index space (an empty hole leaves every vector live) with the gradient options in
+// front of adam_update.  The clamp and the device scale are exact no-ops when off (g * 1.0f == g), and the element then goes
+// through adam_update / ema_update as in the four entry points this generalises: the same bits.
+struct GradOpts { const float* gscale_dev; float clipvalue; };
+
+__device__ __forceinline__ float grad_clamp(float g, float c) { return c > 0.f ? fminf(fmaxf(g, -c), c) : g; }
+
+template <bool EMA, bool HOLE>
+__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 long long n, long long ex_lo, long long ex_hi, const float* __restrict__ lr_t_dev, float b1, float b2,
+                                 float eps, GradOpts o, EmaArgs ema) {
+    const float lr_t = lr_t_dev[0];
+    const float gscale = o.gscale_dev ? o.gscale_dev[0] : 1.0f;
+    const float c = o.clipvalue;
+    float omb = 0.f;
+    if constexpr (EMA) omb = ema_one_minus_beta(ema);
+    // HOLE = false (ex_lo == ex_hi): adam_flat_dev_kernel's plain index space, and its register footprint -- the early Adam over
+    // the generator's head buckets runs beside the weight-gradient stream's last kernels and must leave them room
+    const long long hv_lo = HOLE ? (ex_lo + 3) / 4 : 0, hv_hi = HOLE ? ex_hi / 4 : 0;
+    const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
+    const long long live = n / 4 - hole;
+    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; q < live; q += stride) {
+        const long long i = (!HOLE || q < hv_lo ? q : q + hole) * 4;
+        if (!HOLE || i + 4 <= ex_lo || i >= ex_hi) {
+            f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pi[k], mk = mi[k], vk = vi[k];
+                adam_update(pk, grad_clamp(gi[k], c), mk, vk, lr_t, b1, b2, eps, gscale);
+                pi[k] = pk; mi[k] = mk; vi[k] = vk;
+            }
+            *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
+            if constexpr (EMA) {
+                f32x4 ei = *(const f32x4*)(ema.e + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float ek = ei[k];
+                    ema_update(ek, pi[k], omb);
+                    ei[k] = ek;
+                }
+                *(f32x4*)(ema.e + i) = ei;
+            }
+        } else {
+            for (long long j = i; j < i + 4; ++j)
+                if (j < ex_lo || j >= ex_hi) {
+                    adam_update(p[j], grad_clamp(g[j], c), m[j], v[j], lr_t, b1, b2, eps, gscale);
+                    if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
+                }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = n / 4 * 4; j < n; ++j)
+            if (j < ex_lo || j >= ex_hi) {
+                adam_update(p[j], grad_clamp(g[j], c), m[j], v[j], lr_t, b1, b2, eps, gscale);
+                if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
+            }
+}
+
+extern "C" int p2p_adam_step(const p2p_adam_args* a, void* stream) {
+    P2P_REQUIRE(a && a->hyper, "p2p_adam_step: null argument struct");
+    P2P_REQUIRE(a->p && a->g && a->m && a->v && a->n > 0 && a->lr_t_dev, "p2p_adam_step: bad args");
+    P2P_REQUIRE(0 <= a->ex_lo && a->ex_lo <= a->ex_hi && a->ex_hi <= a->n, "p2p_adam_step: the excluded range must lie inside [0, n)");
+    P2P_REQUIRE(!a->e || a->t_dev, "p2p_adam_step: the moving average needs t_dev");
+    P2P_REQUIRE(((uintptr_t)a->p % 16) == 0 && ((uintptr_t)a->g % 16) == 0 && ((uintptr_t)a->m % 16) == 0 &&
+                    ((uintptr_t)a->v % 16) == 0 && ((uintptr_t)a->e % 16) == 0,
+                "p2p_adam_step: buffers must be 16-byte aligned");
+    const p2p_adam_hyper h = *a->hyper;
+    const long long hv_lo = (a->ex_lo + 3) / 4, hv_hi = a->ex_hi / 4;
+    const long long live = a->n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
+    long long blocks = (live + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    const GradOpts o = {a->gscale_dev, h.clipvalue};
+    const EmaArgs ema = a->e ? EmaArgs{a->e, a->t_dev, h.ema_decay, a->ema_warmup} : EmaArgs{nullptr, nullptr, 0.f, 0};
+    const dim3 grid((unsigned)blocks);
+    const hipStream_t st = (hipStream_t)stream;
+#define ADAM_STEP_LAUNCH(EMA, HOLE)                                                                                                \
+    adam_step_kernel<EMA, HOLE><<<grid, 256, 0, st>>>(a->p, a->g, a->m, a->v, a->n, a->ex_lo, a->ex_hi, a->lr_t_dev, h.beta1, h.beta2, \
+                                                      h.eps, o, ema)
+    const bool holed = a->ex_hi > a->ex_lo;
+    if (a->e && holed) ADAM_STEP_LAUNCH(true, true);
+    else if (a->e) ADAM_STEP_LAUNCH(true, false);
+    else if (holed) ADAM_STEP_LAUNCH(false, true);
+    else ADAM_STEP_LAUNCH(false, false);
+#undef ADAM_STEP_LAUNCH
+    return p2p_check_launch("p2p_adam_step");
+}
+
 __global__ void counter_add_kernel(long long* c, long long inc) { c[0] += inc; }
 
 extern "C" int p2p_counter_add(long long* counter_dev, long long inc, void* stream) {

@@ -263,6 +263,63 @@ class _NullCtx:
         return False
 
 
+class OptimSlots:
+    """One optimizer's settings as ctypes objects the entry points receive BY ADDRESS -- a recorded step reads
+    them when it is replayed, so one recording serves every value: the rate, beta_1, beta_2 (c_float, p2p_adam_tick and the four
+    flat Adam entry points), the schedule (p2p_lr_schedule, p2p_adam_tick_sched), the shared fields of p2p_adam_step's argument
+    struct (p2p_adam_hyper: the betas and epsilon again, the clipvalue, the decay of the average) and the clipnorm threshold.
+    What changes the CALL LIST -- a schedule the device evaluates, either kind of clipping -- is in `key()`, part of the
+    engine's replay key.  The device buffers of the global norm exist once global_clipnorm has been set."""
+
+    def __init__(self, device):
+        self.device = device
+        self.lr, self.b1, self.b2, self.eps, self.clipnorm = C.c_float(), C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self.hyper, self.sched = L.AdamHyper(), L.LrSchedule()
+        self.schedule = None            # the schedule object behind `sched` (None: the plain rate `lr`)
+        self.partials = self.scale_dev = self.norm_dev = None
+        self.parts, self.nparts = (C.c_void_p * 1)(), (C.c_int * 1)()
+        self.set_learning_rate(2e-4)
+        self.set("beta1", 0.5), self.set("beta2", 0.999), self.set("eps", 1e-7)        # pix2pix_model.py:28-29
+
+    scheduled = property(lambda self: self.schedule is not None)
+    clipnorm_on = property(lambda self: self.clipnorm.value > 0)
+    clipvalue_on = property(lambda self: self.hyper.clipvalue > 0)
+    clipped = property(lambda self: self.clipnorm_on or self.clipvalue_on)
+
+    def key(self):
+        return self.clipnorm_on, self.clipvalue_on, self.scheduled
+
+    def set(self, name, v):
+        """beta1 / beta2 / eps: the c_float slot and the struct field"""
+        getattr(self, {"beta1": "b1", "beta2": "b2", "eps": "eps"}[name]).value = v
+        setattr(self.hyper, name, v)
+
+    def set_learning_rate(self, learning_rate):
+        """a float, or a schedule object of schedules.py (written into the p2p_lr_schedule slot in place)"""
+        from .schedules import as_schedule
+        sched, on_device = as_schedule(learning_rate)
+        sched.fill(self.sched)
+        self.lr.value = sched(0)
+        self.schedule = sched if on_device else None
+
+    def learning_rate_at(self, step):
+        """the rate of the step that follows `step` completed ones (f64 on the host, the device's formulas)"""
+        return self.schedule(step) if self.schedule is not None else float(self.lr.value)
+
+    def set_clipping(self, clipvalue=None, global_clipnorm=None):
+        for name, v in (("clipvalue", clipvalue), ("global_clipnorm", global_clipnorm)):
+            if v is not None and not float(v) > 0:
+                raise ValueError(f"{name} must be positive, got {v}")
+        if clipvalue is not None and global_clipnorm is not None:
+            raise ValueError("clipvalue and global_clipnorm together: Keras versions disagree on their order; set one")
+        self.hyper.clipvalue = 0.0 if clipvalue is None else float(clipvalue)
+        self.clipnorm.value = 0.0 if global_clipnorm is None else float(global_clipnorm)
+        if global_clipnorm is not None and self.partials is None:
+            self.partials = torch.zeros(L.SUMSQ_MAX_PARTS, dtype=torch.float32, device=self.device)
+            self.scale_dev = torch.ones(1, dtype=torch.float32, device=self.device)
+            self.norm_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+
 class Pix2PixEngine:
     """One generator + one discriminator + their optimizers on one GPU."""
 
@@ -302,11 +359,13 @@ class Pix2PixEngine:
         # Adam's hyper-parameters and the dropout seed live in ctypes slots (properties below): the entry points receive the slot
         # object, ctypes -- and a replayed step -- read it when the call is issued, so ONE recorded step serves every value of a
         # learning-rate schedule
-        self._slot_lr, self._slot_b1, self._slot_b2, self._slot_eps = C.c_float(), C.c_float(), C.c_float(), C.c_float()
-        self.lr, self.beta1, self.beta2, self.adam_eps = 2e-4, 0.5, 0.999, 1e-7   # pix2pix_model.py:28-29
+        # learning-rate schedule.  Each network's optimizer has its own set (OptimSlots); the properties
+        # lr / beta1 / beta2 / adam_eps below set both and read the generator's
+        self.G.opt, self.D.opt = OptimSlots(self.device), OptimSlots(self.device)
         # moving average of the generator's masters (enable_ema): G.ema is None while it is off.  The decay
         # is a slot like lr; the warm-up flag travels by value and is part of the replay key
-        self._slot_ema, self._ema_warmup = C.c_float(0.999), 1
+        self._slot_ema, self._ema_warmup = C.c_float(), 1
+        self.ema_decay = 0.999
         self._ema_syncs = 0             # times G.ema was written from outside an optimizer step
         self._ema_G = self._ema_W = self._ema_table = self._ema_prepped = None      # the averaged operand copies (averaged())
         self._averaged = False          # inside averaged(): self.G / self.W are the averaged set
@@ -355,10 +414,30 @@ class Pix2PixEngine:
             getattr(self, slot).value = v
         return property(get, put)
 
-    lr, beta1, beta2 = _slot_property("_slot_lr"), _slot_property("_slot_b1"), _slot_property("_slot_b2")
-    adam_eps, seed = _slot_property("_slot_eps"), _slot_property("_slot_seed")
-    ema_decay = _slot_property("_slot_ema")
+    seed = _slot_property("_slot_seed")
     del _slot_property
+
+    def _both_property(name):
+        """a hyper-parameter of both optimizers: reads the generator's, sets both (a store's own: store.opt)"""
+        def get(self):
+            return self.G.opt.learning_rate_at(self.G.t) if name == "lr" else getattr(self.G.opt.hyper, name)
+
+        def put(self, v):
+            for store in (self.G, self.D):
+                store.opt.set_learning_rate(v) if name == "lr" else store.opt.set(name, v)
+        return property(get, put)
+
+    lr, beta1, beta2, adam_eps = _both_property("lr"), _both_property("beta1"), _both_property("beta2"), _both_property("eps")
+    del _both_property
+
+    @property
+    def ema_decay(self):
+        return self._slot_ema.value
+
+    @ema_decay.setter
+    def ema_decay(self, v):
+        self._slot_ema.value = v                # the four flat entry points' argument
+        self.G.opt.hyper.ema_decay = v          # p2p_adam_step's
 
     # ------------------------------------------------------------------ averaged generator (DESIGN.md section 6f)
     @property
@@ -459,8 +538,18 @@ class Pix2PixEngine:
     def _adam_flat(self, store, grads, lo, hi, ex=None):
         """One flat Adam launch over the elements [lo, hi) of a store (ex: a hole, absolute elements), the generator's with its
         moving average folded in while averaging is on: the same launch count either way."""
+        opt = store.opt
         bufs = (_p(store.params, lo), _p(grads, lo), _p(store.m, lo), _p(store.v, lo))
-        hyper = (_p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0)
+        if opt.clipped:
+            # gradient clipping (DESIGN.md section 6h): the struct form of the launch, the scale p2p_clip_scale left on the device
+            ema = store is self.G and store.ema is not None
+            a = L.AdamArgs(bufs[0].value, bufs[1].value, bufs[2].value, bufs[3].value, _p(store.ema, lo).value if ema else None,
+                           hi - lo, ex[0] - lo if ex else 0, ex[1] - lo if ex else 0, store.lr_t_dev.data_ptr(),
+                           opt.scale_dev.data_ptr() if opt.clipnorm_on else None, store.t_dev.data_ptr(),
+                           C.pointer(opt.hyper), self._ema_warmup if ema else 0, 0)
+            L.call("p2p_adam_step", C.byref(a), _stream())
+            return
+        hyper = (_p(store.lr_t_dev), opt.b1, opt.b2, opt.eps, 1.0)
         if store is self.G and store.ema is not None:
             ema = (_p(store.t_dev), self._slot_ema, self._ema_warmup)
             if ex is None:
@@ -471,6 +560,43 @@ class Pix2PixEngine:
             L.call("p2p_adam_flat_dev", *bufs, hi - lo, *hyper, _stream())
         else:
             L.call("p2p_adam_flat_dev_excl", *bufs, hi - lo, ex[0] - lo, ex[1] - lo, *hyper, _stream())
+
+    def _adam_tick(self, store):
+        """t_dev += 1 and the bias-corrected step size of this step, the rate from the store's schedule where the device has one to
+        evaluate (p2p_adam_tick_sched reads the step number on the device: a recorded or captured step follows the schedule)"""
+        opt = store.opt
+        if opt.scheduled:
+            L.call("p2p_adam_tick_sched", _p(store.t_dev), _p(store.lr_t_dev), C.byref(opt.sched), opt.b1, opt.b2, _stream())
+        else:
+            L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), opt.lr, opt.b1, opt.b2, _stream())
+
+    def _clip_scale(self, store, grads):
+        """global_clipnorm: the L2 norm of the store's whole flat gradient (final by now: behind the weight-gradient stream's join
+        and, data parallel, behind the all-reduce -- every rank sums the same values in the same order and gets the same scale,
+        no collective) and the scale the store's Adam launches multiply by.  Two launches; the dead bottleneck's kernel is a hole
+        where the step elides it."""
+        opt = store.opt
+        if not opt.clipnorm_on:
+            return
+        ex = self._frozen if (self._elide >= 2 and store is self.G) else (0, 0)
+        opt.parts[0] = opt.partials.data_ptr()
+        L.call("p2p_sumsq_partials", _p(grads), store.numel, ex[0], ex[1], _p(opt.partials), opt.nparts, _stream())
+        L.call("p2p_clip_scale", opt.parts, opt.nparts, 1, opt.clipnorm, _p(opt.scale_dev), _p(opt.norm_dev), _stream())
+
+    def set_optimizer(self, store, learning_rate=None, beta1=None, beta2=None, eps=None, clipping=None):
+        """One optimizer's settings (store: self.G or self.D); None leaves a setting alone.  learning_rate: a float or a schedule of
+        schedules.py; clipping: (clipvalue or None, global_clipnorm or None).  Values are slots and take effect at the next step,
+        recorded or not; what changes the call list (clipping on / off, a schedule for the device) keys a recording of its own."""
+        opt = store.opt
+        if learning_rate is not None:
+            opt.set_learning_rate(learning_rate)
+        for name, v in (("beta1", beta1), ("beta2", beta2), ("eps", eps)):
+            if v is not None:
+                opt.set(name, v)
+        if clipping is not None:
+            if self.fuse_adam and any(c is not None for c in clipping):
+                raise ValueError("gradient clipping with fuse_adam=True: p2p_adam_prep_batched takes no gradient scale")
+            opt.set_clipping(*clipping)
 
     # ------------------------------------------------------------------ parameters
     def _init_params(self):
@@ -598,7 +724,7 @@ class Pix2PixEngine:
             return
         store = self.D if part == "D" else self.G
         L.call("p2p_adam_prep_batched", self.dtype, n_elems, _p(raw), ntasks, total, _p(store.params), _p(store.grads), _p(store.m),
-               _p(store.v), _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, _stream())
+               _p(store.v), _p(store.lr_t_dev), store.opt.b1, store.opt.b2, store.opt.eps, _stream())
 
     def refresh_weight_copies(self, part="all", outside=True, optimizer_step=False):
         """Re-derives the per-layer weight copies from the f32 masters; runs after every Adam step (one launch per part).
@@ -1071,13 +1197,15 @@ class Pix2PixEngine:
         # everything the recorded calls hold BY VALUE: the switches that choose kernels and K-split / grid targets (SWITCHES) and the stream
         # the step was issued on (raw handle inside the records -- the id of the torch stream object rides along, so a recycled
         # handle value of a NEW stream does not match an old recording).  Adam's hyper-parameters and the dropout seed are NOT
-        # part of the key: the records hold the address of their slots (_slot_lr ...), one recording serves every value.
+        # part of the key: the records hold the address of their slots (OptimSlots), one recording serves every value.  What an
+        # optimizer option changes in the call list is: per network, clipnorm on, clipvalue on, a schedule for the device.
         # Averaging changes the generator's Adam entry points: None while it is off, else the warm-up flag (held by value; the
         # decay is a slot, and the kernels read the step number from G.t_dev).
         st = torch.cuda.current_stream()
         ema = None if self.G.ema is None else int(self._ema_warmup)
         return (kind, B, _SWITCH_VALUES(self), self.use_mfma, self.side.enabled, self.side_hist.enabled,
-                int(st.cuda_stream), int(st.stream_id), int(self._elide), None if dp is None else id(dp), ema) + extra
+                int(st.cuda_stream), int(st.stream_id), int(self._elide), None if dp is None else id(dp), ema,
+                self.G.opt.key(), self.D.opt.key()) + extra
 
     def _bind_batch(self, src_t, real_t):
         """the batch tensors of this step behind the re-usable pointer slots the recorded calls hold"""
@@ -1171,7 +1299,7 @@ class Pix2PixEngine:
             if apply_update:
                 L.call("p2p_counter_add", _p(self.mask_counter_dev), 1, _stream())
                 for store in (self.G, self.D):
-                    L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
+                    self._adam_tick(store)
                 self._ticked = True
             P["early_masks"] = masks is None
             P["early_ev"] = None
@@ -1622,9 +1750,12 @@ class Pix2PixEngine:
         """Single-GPU steps: the main stream finishes the backward pass ~70 us before the weight-gradient stream does (the
         last layers' weight gradients are issued last).  Adam on the part of the generator's flat buffer whose gradients
         are already complete -- everything in front of the last bucket, 90 % of the parameters -- runs in that window: a
-        memory-bound kernel next to the compute-bound tail of the other stream.  Returns the first element still to update."""
+        memory-bound kernel next to the compute-bound tail of the other stream.  Returns the first element still to update.
+        A generator under global_clipnorm has no early part (returns 0): its gradient scale is a function of the WHOLE gradient,
+        which exists only once the last bucket and the small-tensor tail are complete (apply_adam takes the norm there), so the
+        step loses this overlap.  clipvalue alone or a schedule keep it; the discriminator never had one."""
         ev, self._adam_head_ev = self._adam_head_ev, None
-        if not apply_update or not self._ticked or len(self.G.buckets) < 2:
+        if not apply_update or not self._ticked or len(self.G.buckets) < 2 or self.G.opt.clipnorm_on:
             return 0
         if self._dp is not None:
             # data parallel: the buckets in front of the last one were all-reduced asynchronously during the backward pass;
@@ -1653,11 +1784,13 @@ class Pix2PixEngine:
         first generator element not yet updated by _adam_head."""
         self._require_live("an optimizer step")
         ticked, self._ticked = self._ticked, False      # counters already advanced by _early_side of this step
+        if self.fuse_adam and (self.G.opt.clipped or self.D.opt.clipped):
+            raise ValueError("gradient clipping with fuse_adam=True: p2p_adam_prep_batched takes no gradient scale")
         if self.fuse_adam:
             for store in (self.G, self.D):
                 store.t += 1
                 if not ticked:
-                    L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
+                    self._adam_tick(store)
             if g_from == 0:
                 self._adam_prep("G_head")
             self._adam_prep("G_rest")
@@ -1666,7 +1799,7 @@ class Pix2PixEngine:
                 lo_e, hi_e = store.small_range
                 if hi_e > lo_e:
                     L.call("p2p_adam_flat_dev", _p(store.params, lo_e), _p(store.grads, lo_e), _p(store.m, lo_e), _p(store.v, lo_e),
-                           hi_e - lo_e, _p(store.lr_t_dev), self._slot_b1, self._slot_b2, self._slot_eps, 1.0, _stream())
+                           hi_e - lo_e, _p(store.lr_t_dev), store.opt.b1, store.opt.b2, store.opt.eps, 1.0, _stream())
             if self.G.ema is not None:
                 # the tiled Adam kernels do not average: one pass of its own over the whole generator, behind all of them
                 L.call("p2p_ema_flat", _p(self.G.ema), _p(self.G.params), self.G.numel, _p(self.G.t_dev), self._slot_ema,
@@ -1681,7 +1814,8 @@ class Pix2PixEngine:
         for store in (self.G, self.D):
             store.t += 1
             if not ticked:
-                L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
+                self._adam_tick(store)
+            self._clip_scale(store, store.grads)
             self._adam_range(store, g_from if store is self.G else 0, store.numel)
         if not ticked:
             L.call("p2p_counter_add", _p(self.mask_counter_dev), 1, _stream())
@@ -2191,6 +2325,7 @@ class Pix2PixEngine:
         form for both networks; the dropout counter is not advanced here (a tape's generator calls advance it)."""
         self._require_live("an optimizer step")
         store.t += 1
-        L.call("p2p_adam_tick", _p(store.t_dev), _p(store.lr_t_dev), self._slot_lr, self._slot_b1, self._slot_b2, _stream())
+        self._adam_tick(store)
+        self._clip_scale(store, grads)
         self._adam_flat(store, grads, 0, store.numel)
         self.refresh_weight_copies("G" if store is self.G else "D", optimizer_step=True)

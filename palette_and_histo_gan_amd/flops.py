@@ -180,6 +180,13 @@ def call_work(name, args, dtype):
         return {"flops": 0.0, "mfma": None, "bytes": 9 * 4.0 * int(args[5])}
     if name == "p2p_adam_ema_flat_dev_excl":
         return {"flops": 0.0, "mfma": None, "bytes": 9 * 4.0 * (int(args[5]) - (int(args[7]) - int(args[6])))}
+    if name == "p2p_adam_step":               # the struct form: the same streams, the hole and the average as its fields say
+        a = getattr(args[0], "_obj", args[0])
+        return {"flops": 0.0, "mfma": None, "bytes": (9 if a.e else 7) * 4.0 * (int(a.n) - (int(a.ex_hi) - int(a.ex_lo)))}
+    if name == "p2p_sumsq_partials":          # one read of the gradient (the hole's whole vectors are skipped)
+        return {"flops": 0.0, "mfma": None, "bytes": 4.0 * (int(args[1]) - (int(args[3]) - int(args[2])))}
+    if name == "p2p_clip_scale":              # at most 8 x 1024 partials: nothing beside the gradient read
+        return {"flops": 0.0, "mfma": None, "bytes": 4.0 * 1024 * int(args[2])}
     if name == "p2p_ema_flat":                # p, e in; e out
         return {"flops": 0.0, "mfma": None, "bytes": 3 * 4.0 * int(args[2])}
     if name == "p2p_adam_prep_batched":       # g, m, v, theta in; m, v, theta out; two operand copies out

@@ -21,8 +21,12 @@ reference's signatures for standalone evaluation.  A SUBCLASS that overrides one
 train_step detects the override and runs the hooked step instead (hooks under torch autograd, gradients into the backward
 kernels); the palette-index model takes that path only when the subclass sets `differentiable_loss_hooks = True`, and raises
 otherwise instead of silently ignoring the override.
-Extra keyword arguments (dtype, img_size, device, data_parallel, seed, ema_decay, ema_warmup) are build-added; defaults reproduce
-the reference.
+Extra keyword arguments (dtype, img_size, device, data_parallel, seed, ema_decay, ema_warmup, generator_optimizer,
+discriminator_optimizer) are build-added; defaults reproduce the reference.
+
+Optimizers (build-added): generator_optimizer= / discriminator_optimizer= (or an overridden create_optimizers())
+replace the reference's two Adam(0.0002, beta_1=0.5); each may have its own rate or learning-rate schedule, betas, epsilon,
+clipvalue or global_clipnorm, and its attributes stay live after construction.
 
 Averaged generator (build-added): with `ema_decay` (e.g. 0.999) the engine keeps an exponential moving average
 of the generator's weights, updated inside the Adam launch of every step.  Training is unchanged; generate(), the previews,
@@ -90,11 +94,87 @@ class CategoricalCrossentropy:
 
 class Adam:
     """tf.keras.optimizers.Adam(learning_rate, beta_1) as the reference constructs it (pix2pix_model.py:28-29): the
-    hyper-parameters live here, the moments and the step count in the engine's flat buffers (engine.ParamStore)."""
+    hyper-parameters live here, the moments and the step count in the engine's flat buffers (engine.ParamStore).
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+    Options, each optimizer its own:
+      learning_rate    a float or a schedule of palette_and_histo_gan_amd.schedules (tf_compat.tf.keras.optimizers.schedules.*),
+                       evaluated on the device from `iterations`
+      clipvalue        every gradient element is clamped to [-clipvalue, clipvalue]
+      global_clipnorm  the network's whole gradient is scaled by global_clipnorm / ||g||_2 where the norm exceeds it
+                       (tf.clip_by_global_norm); `last_global_norm` is the norm of the last step, a device scalar
+    Once a model has bound the optimizer, assigning learning_rate / beta_1 / beta_2 / epsilon / clipvalue / global_clipnorm writes
+    through to the engine and holds from the next step on.  Per-variable `clipnorm`, `weight_decay` and `amsgrad` are not built."""
+
+    _SETTINGS = ("learning_rate", "beta_1", "beta_2", "epsilon", "clipvalue", "global_clipnorm")
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipvalue=None, global_clipnorm=None, **kwargs):
+        from .schedules import as_schedule
+        supported = "supported: learning_rate (float or schedule), beta_1, beta_2, epsilon, clipvalue, global_clipnorm"
+        for name in ("clipnorm", "weight_decay", "amsgrad"):
+            if kwargs.pop(name, None):
+                raise NotImplementedError(f"Adam({name}=...) is not built; {supported}")
+        if kwargs:
+            raise TypeError(f"Adam got unexpected keyword arguments {sorted(kwargs)}; {supported}")
+        for name, v in (("clipvalue", clipvalue), ("global_clipnorm", global_clipnorm)):
+            if v is not None and not float(v) > 0:
+                raise ValueError(f"{name} must be positive, got {v}")
+        if clipvalue is not None and global_clipnorm is not None:
+            raise ValueError("clipvalue and global_clipnorm together: Keras versions disagree on their order; set one")
+        as_schedule(learning_rate)
         self._store = self._engine = None
+        self._values = dict(zip(self._SETTINGS, (learning_rate, beta_1, beta_2, epsilon, clipvalue, global_clipnorm)))
+
+    def _setting(name):
+        def get(self):
+            return self._values[name]
+
+        def put(self, v):
+            old = self._values[name]
+            self._values[name] = v
+            try:
+                self._push(name)
+            except Exception:
+                self._values[name] = old
+                raise
+        return property(get, put)
+
+    learning_rate, beta_1, beta_2 = _setting("learning_rate"), _setting("beta_1"), _setting("beta_2")
+    epsilon, clipvalue, global_clipnorm = _setting("epsilon"), _setting("clipvalue"), _setting("global_clipnorm")
+    del _setting
+
+    def _push(self, name=None):
+        """writes one setting (None: all) into the engine's slots of this optimizer's network"""
+        eng, store, v = self._engine, self._store, self._values
+        if store is None:
+            if name in ("clipvalue", "global_clipnorm") and v["clipvalue"] is not None and v["global_clipnorm"] is not None:
+                raise ValueError("clipvalue and global_clipnorm together: Keras versions disagree on their order; set one")
+            return
+        if name in (None, "learning_rate"):
+            eng.set_optimizer(store, learning_rate=v["learning_rate"])
+        if name in (None, "beta_1", "beta_2", "epsilon"):
+            eng.set_optimizer(store, beta1=v["beta_1"], beta2=v["beta_2"], eps=v["epsilon"])
+        if name in (None, "clipvalue", "global_clipnorm"):
+            eng.set_optimizer(store, clipping=(v["clipvalue"], v["global_clipnorm"]))
+
+    def _bind(self, engine, store):
+        self._engine, self._store = engine, store
+        self._push()
+
+    def get_config(self):
+        """the settings as plain values (a schedule as its repr): what a checkpoint records"""
+        return {k: (v if v is None or isinstance(v, (int, float)) else repr(v)) for k, v in self._values.items()}
+
+    @property
+    def last_global_norm(self):
+        """the L2 norm of the whole gradient at this optimizer's last step, as a device scalar (no synchronisation); None without
+        global_clipnorm"""
+        opt = None if self._store is None else self._store.opt
+        return opt.norm_dev[0] if opt is not None and opt.clipnorm_on else None
+
+    def current_learning_rate(self):
+        """the rate of the next step: the schedule at `iterations` (f64 on the host, the device's formulas)"""
+        from .schedules import as_schedule
+        return float(as_schedule(self._values["learning_rate"])[0](self.iterations))
 
     @property
     def iterations(self):
@@ -137,7 +217,8 @@ class Adam:
 
 class Pix2PixModel(S2SModel):
     def __init__(self, train_ds, test_ds, model_name, architecture_name, lambda_l1, dtype="bf16", img_size=IMG_SIZE,
-                 device="cuda:0", data_parallel=None, seed=None, ema_decay=None, ema_warmup=True):
+                 device="cuda:0", data_parallel=None, seed=None, ema_decay=None, ema_warmup=True, generator_optimizer=None,
+                 discriminator_optimizer=None):
         super().__init__(train_ds, test_ds, model_name, architecture_name)
         if seed is None:
             from .tf_compat import global_seed      # configuration.SEED unless the notebook's tf.random.set_seed changed it
@@ -153,8 +234,13 @@ class Pix2PixModel(S2SModel):
         self.generator = self.create_generator()
         self.discriminator = self.create_discriminator()
         self.loss_object = BinaryCrossentropy(from_logits=True)
-        self.generator_optimizer = Adam(0.0002, beta_1=0.5)
-        self.discriminator_optimizer = Adam(0.0002, beta_1=0.5)
+        self.generator_optimizer, self.discriminator_optimizer = self.create_optimizers()
+        if generator_optimizer is not None:
+            self.generator_optimizer = generator_optimizer
+        if discriminator_optimizer is not None:
+            self.discriminator_optimizer = discriminator_optimizer
+        if self.generator_optimizer is self.discriminator_optimizer:
+            raise ValueError("the two networks need an optimizer object each (each holds its own step count and moments)")
         self.engine = self.create_engine()
 
         print(f"Generator: {self.generator.name} with {self.generator.count_params():,} parameters")
@@ -174,6 +260,11 @@ class Pix2PixModel(S2SModel):
     def create_discriminator(self):
         return PatchDiscriminator(4)
 
+    def create_optimizers(self):
+        """build-added: (generator optimizer, discriminator optimizer), the reference's pair (pix2pix_model.py:28-29) unless
+        overridden; the constructor keywords generator_optimizer= / discriminator_optimizer= replace either"""
+        return Adam(0.0002, beta_1=0.5), Adam(0.0002, beta_1=0.5)
+
     def create_engine(self):
         """build-added: one device engine for both networks, from the architecture the two builders recorded"""
         g, d = self.generator, self.discriminator
@@ -182,13 +273,10 @@ class Pix2PixModel(S2SModel):
         eng = Pix2PixEngine(g.input_channels, g.output_channels, g.last_activation, self._img_size, self._dtype,
                             device=self._device, seed=self._seed)
         go, do = self.generator_optimizer, self.discriminator_optimizer
-        if (go.learning_rate, go.beta_1, go.beta_2, go.epsilon) != (do.learning_rate, do.beta_1, do.beta_2, do.epsilon):
-            raise NotImplementedError("both optimizers share one set of Adam hyper-parameters (as in the reference)")
-        eng.lr, eng.beta1, eng.beta2, eng.adam_eps = go.learning_rate, go.beta_1, go.beta_2, go.epsilon
         g.bind(eng, eng.G)
         d.bind(eng, eng.D)
-        go._store, do._store = eng.G, eng.D
-        go._engine = do._engine = eng
+        go._bind(eng, eng.G)        # each optimizer's settings into its network's slots (they may differ in everything)
+        do._bind(eng, eng.D)
         if self.ema_decay is not None:
             eng.enable_ema(self.ema_decay, self.ema_warmup)
         if self.data_parallel is not None:
@@ -312,6 +400,17 @@ class Pix2PixModel(S2SModel):
         s = int(step) // int(update_steps)
         self.log_generator_loss(g_loss, s)
         self.log_discriminator_loss(d_loss, s)
+        self.log_optimizers(s)
+
+    def log_optimizers(self, step):
+        """build-added: the rate of the step just taken for an optimizer with a schedule, the gradient norm (device scalar, no
+        synchronisation) for one with global_clipnorm; the reference's optimizers log nothing (the same event files as before)"""
+        from .schedules import LearningRateSchedule
+        for tag, opt in (("generator", self.generator_optimizer), ("discriminator", self.discriminator_optimizer)):
+            if isinstance(opt.learning_rate, LearningRateSchedule):
+                self.summary_writer.scalar(f"{tag}/learning_rate", float(opt.learning_rate(max(opt.iterations - 1, 0))), step)
+            if opt.last_global_norm is not None:
+                self.summary_writer.scalar(f"{tag}/gradient_norm", opt.last_global_norm.clone(), step)
 
     def log_generator_loss(self, g_loss, step):
         """pix2pix_model.py:91-95"""

@@ -105,7 +105,19 @@ class Checkpoint:
         if e.G.ema is not None:         # the averaged generator (engine.enable_ema): only a model that keeps one writes the keys
             st["G.ema"] = e.G.ema.cpu()
             st["ema"] = (float(e.ema_decay), bool(e._ema_warmup))
+        # the optimizers' settings, informative (the rate is a function of the step counts above); as with the average, only a model
+        # that departs from the reference's pair writes the key: default checkpoints keep their set of keys
+        settings = self._optimizer_settings()
+        if any(cfg != self._REFERENCE_ADAM for cfg in settings.values()):
+            st["optimizer"] = settings
         return st
+
+    _REFERENCE_ADAM = {"learning_rate": 0.0002, "beta_1": 0.5, "beta_2": 0.999, "epsilon": 1e-7, "clipvalue": None,
+                       "global_clipnorm": None}          # pix2pix_model.py:28-29
+
+    def _optimizer_settings(self):
+        return {k: o.get_config() for k, o in (("generator", self.generator_optimizer), ("discriminator", self.discriminator_optimizer))
+                if hasattr(o, "get_config")}
 
     def save(self, path):
         torch.save(self.state(), path)
@@ -115,9 +127,16 @@ class Checkpoint:
         """weights, both Adam states (moments and step counts), the dropout counter and the generator's moving average, so that
         the next step is the one that would have followed the save.  A checkpoint without an average restarts the average of a
         model that keeps one from the restored weights; one with an average is accepted by a model that keeps none (ignored).
-        The decay and the warm-up flag stay the model's own: the stored pair is informative."""
+        The decay and the warm-up flag stay the model's own: the stored pair is informative.  So are the optimizers' settings
+        (rate or schedule, betas, epsilon, clipping): a checkpoint written under other settings is accepted, with one warning."""
         ck = torch.load(path, map_location="cpu")
         e = self.engine
+        stored = ck.get("optimizer", {k: self._REFERENCE_ADAM for k in self._optimizer_settings()})
+        if stored != self._optimizer_settings() and not getattr(self, "_warned_settings", False):
+            import warnings
+            self._warned_settings = True
+            warnings.warn(f"{path} was written with other optimizer settings ({stored}); this model's own stay in force "
+                          f"({self._optimizer_settings()})")
         for store, k in ((e.G, "G"), (e.D, "D")):
             store.params.copy_(ck[k])
             store.m.copy_(ck[k + ".m"])

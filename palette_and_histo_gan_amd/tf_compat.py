@@ -8,6 +8,9 @@ imports changed (examples/experiments.py runs the same workflow
 and augmentation draws (dataset_utils.load_rgba_ds / load_indexed_ds) and the models' weight initialisation and dropout
 streams (pix2pix_model.Pix2Pix*Model).  The random streams are numpy's and the device's, not TensorFlow's.
 
+`tf.keras.optimizers.Adam` and `tf.keras.optimizers.schedules.*` are pix2pix_model.Adam and the schedules of schedules.py
+(DESIGN.md section 6h).
+
 `tf.GradientTape(persistent=False)` records the HIP networks' calls for a custom train_step (tape.py).
 """
 from .configuration import SEED
@@ -38,9 +41,24 @@ class _Test:
         return bool(_Test.gpu_device_name())
 
 
+class _Optimizers:
+    """tf.keras.optimizers: Adam (pix2pix_model.Adam) and the learning-rate schedules (schedules.py)"""
+    from . import schedules
+
+    @property
+    def Adam(self):
+        from .pix2pix_model import Adam
+        return Adam
+
+
+class _Keras:
+    optimizers = _Optimizers()
+
+
 class _TF:
     random = _Random()
     test = _Test()
+    keras = _Keras()
     GradientTape = GradientTape
 
     @property
