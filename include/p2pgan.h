@@ -514,6 +514,33 @@ int p2p_palette_extract(int N, int H, int W, const float* img, int cap, int* pal
  * give identical bits).  No workspace, no allocation. */
 int p2p_palette_snap(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, int* index_out,
                      float* image_out, int* dist_out, int* counts_out, long long* stats_out, void* stream);
+/* A palette of at most `colours` colours for every image, derived from the image itself by an integer k-means.
+ * img: dense f32 [N][H][W][4] in [-1, 1], 16-byte aligned; palette_out: int32 [N][K][4], 16-byte aligned; sizes_out: int32 [N];
+ * iters_out: int32 [N] or NULL; init_palette int32 [N][K][4] (16-byte aligned) and init_sizes int32 [N]: both given or both NULL.
+ * 1 <= colours <= K <= 256, 0 <= iterations <= 64, H * W <= 2^14 (128 x 128: an image's keys stay in LDS; larger maps are refused);
+ * anything else returns a negative code and sets p2p_last_error before any launch.  Per image n, with
+ * D(a, b) = sum_c (a_c - b_c)^2 over the four channels, in integers:
+ *   0. q_p = the pixel quantised as p2p_palette_extract / p2p_palette_snap quantise it (NaN -> 0), key = r + 256 g + 65536 b + 2^24 a,
+ *      U = the set of distinct keys of the image.
+ *   1. |U| <= colours: palette_out = the colours of U in ascending key order, sizes_out = |U|, iters_out = 0 -- the bits
+ *      p2p_palette_extract writes with cap = K -- whether or not an initial palette was given.
+ *   2. Starting slots C[0 .. m).  With n0 = clamp(init_sizes[n], 0, K) > 0: m = min(n0, colours), C[k] = init_palette[n][k] & 255 per
+ *      channel (duplicate rows allowed).  Otherwise m = colours by farthest-point selection: C[0] = the colour of the smallest key
+ *      of U; for j = 1 .. m-1 with m_p = min_{i<j} D(q_p, C[i]): C[j] = the colour of a pixel that maximises m_p, among equal maxima
+ *      the one with the lowest key (|U| > colours: every maximum is > 0 and the C[j] are distinct).
+ *   3. Lloyd passes t = 1 .. iterations: a_p = argmin_{k<m} D(q_p, C[k]), ties to the lowest k (p2p_palette_snap's rule, same device
+ *      code); n_k = #{p : a_p = k}, S_kc = sum_{a_p = k} q_pc; C'[k][c] = floor((2 S_kc + n_k) / (2 n_k)) if n_k > 0, a slot without
+ *      pixels keeps its colour; C' = C stops.  iters_out = the number of assignment passes made up to and including the one that
+ *      found the fixed point (`iterations` if none did, 0 for iterations = 0).
+ *   4. palette_out = the distinct keys of the final C in ascending order, unpacked to int32 RGBA rows (rounded centroids can
+ *      coincide and duplicates given in init stay duplicates: possibly fewer than m), sizes_out = their number, rows from sizes_out
+ *      to K zero.  Every element of every output is written.
+ * Integer arithmetic throughout (sums <= 2^14 * 255): the result depends only on the multiset of the image's quantised colours --
+ * not on the order of the pixels, on N, on the image's place in the batch or on how the work is split between lanes -- and two calls
+ * give identical bits.  The centroids are not re-assigned: snap with p2p_palette_snap, which also yields the index image, the
+ * counts and the quantisation error.  One workgroup per image, 17.1 KB + 8 H W bytes of LDS; no workspace, no allocation. */
+int p2p_palette_quantize(int N, int H, int W, const float* img, int colours, int iterations, const int* init_palette,
+                         const int* init_sizes, int K, int* palette_out, int* sizes_out, int* iters_out, void* stream);
 
 /* Differentiable palette projection (DESIGN.md "palette projection"): every pixel replaced by a colour of its image's palette.
  * img, palette, sizes, K, tau and w_pk as for the soft histogram; n = clamp(sizes[n], 0, K); out: dense f32 [N][H][W][4], 16-byte

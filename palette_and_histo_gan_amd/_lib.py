@@ -99,6 +99,7 @@ SIGNATURES = {
     "p2p_palette_loss": [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp],
     "p2p_palette_extract": [_i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "p2p_palette_snap": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "p2p_palette_quantize": [_i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "p2p_palette_project_fwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _vp],
     "p2p_palette_project_bwd": [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
     "p2p_palette_lookup_fwd": [_i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp],

@@ -285,53 +285,74 @@ __device__ __forceinline__ unsigned pal_quant(float v) {
     return (unsigned)fminf(fmaxf(q, 0.f), 255.f);          // fmaxf(NaN, 0) = 0
 }
 
-__global__ __launch_bounds__(PAL_THREADS) void palette_extract_kernel(int HW, const float* __restrict__ img, int cap, int* __restrict__ pal_out,
-                                                                      int* __restrict__ sizes_out) {
-    __shared__ unsigned long long table[PAL_TABLE];
-    __shared__ unsigned keys[PAL_MAX];
-    __shared__ int count, over, m;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < PAL_TABLE; i += PAL_THREADS) table[i] = PAL_EMPTY;
-    if (tid == 0) { count = 0; over = 0; m = 0; }
-    __syncthreads();
-    for (int p = tid; p < HW; p += PAL_THREADS) {
-        if (*(volatile int*)&over) break;
-        const float4 v = *(const float4*)(img + ((long long)b * HW + p) * 4);
-        const unsigned key = pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
-        unsigned slot = (key * 2654435761u) >> 22;          // Fibonacci hash, top 10 bits
-        for (int probe = 0; probe < PAL_TABLE; ++probe) {
-            const unsigned long long seen = atomicCAS(&table[slot], PAL_EMPTY, (unsigned long long)key);
-            if (seen == (unsigned long long)key) break;     // already there
-            if (seen == PAL_EMPTY) {                         // this lane inserted it
-                if (atomicAdd(&count, 1) + 1 > cap) atomicExch(&over, 1);
-                break;
-            }
-            slot = (slot + 1) & (PAL_TABLE - 1);
+// The hash set as device functions (palette_extract_kernel and palette_quantize_kernel share them): clear, then a barrier; insert
+// from any lane; after a barrier `over` says whether more than cap keys arrived, and if not pal_set_rows writes the sorted rows.
+struct PalSet {
+    unsigned long long table[PAL_TABLE];
+    unsigned keys[PAL_MAX];
+    int count, over, m, pad;
+};
+
+__device__ __forceinline__ void pal_set_clear(PalSet* s) {
+    for (int i = threadIdx.x; i < PAL_TABLE; i += PAL_THREADS) s->table[i] = PAL_EMPTY;
+    if (threadIdx.x == 0) { s->count = 0; s->over = 0; s->m = 0; }
+}
+
+__device__ __forceinline__ void pal_set_insert(PalSet* s, unsigned key, int cap) {
+    unsigned slot = (key * 2654435761u) >> 22;          // Fibonacci hash, top 10 bits
+    for (int probe = 0; probe < PAL_TABLE; ++probe) {
+        const unsigned long long seen = atomicCAS(&s->table[slot], PAL_EMPTY, (unsigned long long)key);
+        if (seen == (unsigned long long)key) break;     // already there
+        if (seen == PAL_EMPTY) {                         // this lane inserted it
+            if (atomicAdd(&s->count, 1) + 1 > cap) atomicExch(&s->over, 1);
+            break;
+        }
+        slot = (slot + 1) & (PAL_TABLE - 1);
+    }
+}
+
+// The whole workgroup, with over == 0: the set's keys in ascending order as int32 RGBA rows row[0 .. n), zero rows up to `rows`;
+// returns n.  Holds a barrier.
+__device__ __forceinline__ int pal_set_rows(PalSet* s, int cap, int rows, int* __restrict__ row) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < PAL_TABLE; i += PAL_THREADS) {
+        const unsigned long long e = s->table[i];
+        if (e != PAL_EMPTY) {
+            const int at = atomicAdd(&s->m, 1);               // any order: the ranks below do not depend on it
+            if (at < PAL_MAX) s->keys[at] = (unsigned)e;
         }
     }
     __syncthreads();
+    const int n = s->m < cap ? s->m : cap;                   // m == count <= cap <= PAL_MAX here
+    for (int i = n + tid; i < rows; i += PAL_THREADS) *(int4*)(row + 4 * i) = make_int4(0, 0, 0, 0);
+    if (tid < n) {
+        const unsigned key = s->keys[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += s->keys[j] < key ? 1 : 0;      // keys are distinct
+        *(int4*)(row + 4 * rank) = make_int4((int)(key & 255u), (int)((key >> 8) & 255u), (int)((key >> 16) & 255u), (int)(key >> 24));
+    }
+    return n;
+}
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_extract_kernel(int HW, const float* __restrict__ img, int cap, int* __restrict__ pal_out,
+                                                                      int* __restrict__ sizes_out) {
+    __shared__ PalSet set;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    pal_set_clear(&set);
+    __syncthreads();
+    for (int p = tid; p < HW; p += PAL_THREADS) {
+        if (*(volatile int*)&set.over) break;
+        const float4 v = *(const float4*)(img + ((long long)b * HW + p) * 4);
+        pal_set_insert(&set, pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24), cap);
+    }
+    __syncthreads();
     int* row = pal_out + (long long)b * cap * 4;
-    if (over) {
+    if (set.over) {
         for (int i = tid; i < cap * 4; i += PAL_THREADS) row[i] = 0;
         if (tid == 0) sizes_out[b] = -1;
         return;
     }
-    for (int i = tid; i < PAL_TABLE; i += PAL_THREADS) {
-        const unsigned long long e = table[i];
-        if (e != PAL_EMPTY) {
-            const int at = atomicAdd(&m, 1);                  // any order: the ranks below do not depend on it
-            if (at < PAL_MAX) keys[at] = (unsigned)e;
-        }
-    }
-    __syncthreads();
-    const int n = m < cap ? m : cap;                         // m == count <= cap <= PAL_MAX here
-    for (int i = n + tid; i < cap; i += PAL_THREADS) *(int4*)(row + 4 * i) = make_int4(0, 0, 0, 0);
-    if (tid < n) {
-        const unsigned key = keys[tid];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += keys[j] < key ? 1 : 0;      // keys are distinct
-        *(int4*)(row + 4 * rank) = make_int4((int)(key & 255u), (int)((key >> 8) & 255u), (int)((key >> 16) & 255u), (int)(key >> 24));
-    }
+    const int n = pal_set_rows(&set, cap, cap, row);
     if (tid == 0) sizes_out[b] = n;
 }
 
@@ -353,14 +374,17 @@ __device__ __forceinline__ unsigned pal_snap_quant(const float4& v) {
     return pal_quant(v.x) | (pal_quant(v.y) << 8) | (pal_quant(v.z) << 16) | (pal_quant(v.w) << 24);
 }
 
+__device__ __forceinline__ uint2 pal_snap_slot(unsigned pk, int k) {
+    return make_uint2(pk, ((__builtin_amdgcn_udot4(pk, pk, 0u, false) + PAL_SNAP_BIAS) << 8) | (unsigned)k);
+}
+
 __device__ __forceinline__ int pal_snap_load(const int* __restrict__ palette, const int* __restrict__ sizes, int b, int K, uint2* slot) {
     int n = sizes[b];
     n = n < 0 ? 0 : (n > K ? K : n);
     for (int k = threadIdx.x; k < n; k += PAL_THREADS) {
         const int4 c = *(const int4*)(palette + ((long long)b * K + k) * 4);
         const unsigned cx = (unsigned)c.x & 255u, cy = (unsigned)c.y & 255u, cz = (unsigned)c.z & 255u, cw = (unsigned)c.w & 255u;
-        const unsigned pk = cx | (cy << 8) | (cz << 16) | (cw << 24);
-        slot[k] = make_uint2(pk, ((cx * cx + cy * cy + cz * cz + cw * cw + PAL_SNAP_BIAS) << 8) | (unsigned)k);
+        slot[k] = pal_snap_slot(cx | (cy << 8) | (cz << 16) | (cw << 24), k);
     }
     return n;
 }
@@ -446,6 +470,222 @@ __global__ __launch_bounds__(PAL_THREADS) void palette_snap_kernel(int HW, const
     for (int k = tid; k < n; k += PAL_THREADS)
         if (cnt[k]) atomicAdd(counts + (long long)b * K + k, cnt[k]);
     if (tid < 2 && sums[tid]) atomicAdd((unsigned long long*)(stats + (long long)b * 2 + tid), (unsigned long long)sums[tid]);
+}
+
+// A palette of at most `colours` colours FOR an image, derived from the image itself (the contract is the comment of
+// p2p_palette_quantize in p2pgan.h): farthest-point starting slots, then Lloyd passes, all in integers.  One workgroup per image and
+// everything in dynamic LDS: the scratch below, then the image's packed keys (4 B per pixel) and the running minimum m_p of the
+// farthest-point selection (4 B per pixel) -- 17.1 KB + 8 HW bytes: 49 KB at 64 x 64 (three workgroups per CU), 145 KB at 128 x 128.
+//   exact path:      the bounded hash set of palette_extract_kernel with cap = colours; `over` is read after a barrier.
+//   farthest point:  per step one sweep over the pixels (m_p = min(m_p, D(q_p, C[j-1])), best = max of (m_p << 32) | ~key, i.e. the
+//                    largest m_p and among equals the lowest key), a wave64 butterfly and one barrier: red[] is double-buffered by
+//                    the step's parity, and every lane takes the maximum of the four wave results itself.  Step 0 runs on
+//                    m_p = 2^32 - 1 everywhere, so it returns the lowest key.
+//   Lloyd pass:      the snap's packed-key minimum over slot[] (pal_snap_min), PAL_SNAP_PIX pixels per lane and sweep; per-slot count
+//                    and channel sums are LDS integer atomics.  A sprite is mostly one colour, so lanes that share their slot with
+//                    the first pending lane are summed across the wave first (up to PAL_Q_ROUNDS such groups per sweep, a group of
+//                    fewer than PAL_Q_GROUP lanes is not worth the butterfly) and one lane adds the totals; integer sums, so the
+//                    grouping cannot change a bit.  Then one lane per slot rounds the centroid, raises changed[t & 1] if it moved
+//                    and clears the sums; all lanes read the flag behind a barrier and leave together.
+// Every loop is bounded by HW, colours, iterations or a constant; no barrier stands under a condition that differs between lanes.
+#define PAL_Q_MAXPIX (1 << 14)
+#define PAL_Q_ROUNDS 3
+#define PAL_Q_GROUP 8
+
+struct PalQuantScratch {
+    PalSet set;
+    uint2 slot[PAL_MAX];                                   // x: packed bytes, y: key word (pal_snap_slot)
+    unsigned acc[5][PAL_MAX];                              // n_k and the four channel sums S_k
+    unsigned first[PAL_MAX];                               // 1 where no lower slot holds the same colour
+    unsigned long long red[2][PAL_THREADS / 64];
+    int changed[2], pad[2];
+};
+static_assert(sizeof(PalQuantScratch) % 16 == 0, "the keys behind the scratch stay 16-byte aligned");
+
+__device__ __forceinline__ unsigned pal_q_wave_sum(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// adds pixel q to slot k's count and sums for every lane with `valid`; the whole wave calls it
+__device__ __forceinline__ void pal_q_add(unsigned (*acc)[PAL_MAX], bool valid, unsigned k, unsigned q) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(valid), direct = 0ull;
+#pragma unroll
+    for (int round = 0; round < PAL_Q_ROUNDS; ++round) {
+        if (todo == 0ull) break;                           // wave-uniform, as everything that steers this loop
+        const int leader = __ffsll((long long)todo) - 1;
+        const unsigned lk = __shfl(k, leader, 64);
+        const bool mine = ((todo >> lane) & 1ull) && k == lk;
+        const unsigned long long match = __ballot(mine);
+        todo &= ~match;
+        if (__popcll(match) < PAL_Q_GROUP) {
+            direct |= match;
+            continue;
+        }
+        // two channels per word: 64 lanes * 255 < 2^16
+        const unsigned rg = pal_q_wave_sum(mine ? (q & 255u) | (((q >> 8) & 255u) << 16) : 0u);
+        const unsigned ba = pal_q_wave_sum(mine ? ((q >> 16) & 255u) | ((q >> 24) << 16) : 0u);
+        if (lane == leader) {
+            atomicAdd(&acc[0][lk], (unsigned)__popcll(match));
+            atomicAdd(&acc[1][lk], rg & 0xFFFFu);
+            atomicAdd(&acc[2][lk], rg >> 16);
+            atomicAdd(&acc[3][lk], ba & 0xFFFFu);
+            atomicAdd(&acc[4][lk], ba >> 16);
+        }
+    }
+    if (((todo | direct) >> lane) & 1ull) {
+        atomicAdd(&acc[0][k], 1u);
+        atomicAdd(&acc[1][k], q & 255u);
+        atomicAdd(&acc[2][k], (q >> 8) & 255u);
+        atomicAdd(&acc[3][k], (q >> 16) & 255u);
+        atomicAdd(&acc[4][k], q >> 24);
+    }
+}
+
+__global__ __launch_bounds__(PAL_THREADS) void palette_quantize_kernel(int HW, const float* __restrict__ img, int colours, int iterations,
+                                                                       const int* __restrict__ init_palette, const int* __restrict__ init_sizes,
+                                                                       int K, int* __restrict__ pal_out, int* __restrict__ sizes_out,
+                                                                       int* __restrict__ iters_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pal_q_lds[];
+    PalQuantScratch* s = (PalQuantScratch*)pal_q_lds;
+    unsigned* keys = (unsigned*)(pal_q_lds + sizeof(PalQuantScratch));      // [HW]
+    unsigned* far = keys + HW;                                               // [HW]
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int* row = pal_out + (long long)b * K * 4;
+    // 0: quantise; the set stops taking keys once it holds more than `colours`
+    pal_set_clear(&s->set);
+    if (tid < 2) s->changed[tid] = 0;
+    __syncthreads();
+    for (int p = tid; p < HW; p += PAL_THREADS) {
+        const unsigned key = pal_snap_quant(*(const float4*)(img + ((long long)b * HW + p) * 4));
+        keys[p] = key;
+        far[p] = 0xFFFFFFFFu;
+        if (!*(volatile int*)&s->set.over) pal_set_insert(&s->set, key, colours);
+    }
+    __syncthreads();
+    // 1: at most `colours` colours: they are the palette
+    if (!s->set.over) {                                    // the whole workgroup
+        const int n = pal_set_rows(&s->set, colours, K, row);
+        if (tid == 0) {
+            sizes_out[b] = n;
+            if (iters_out) iters_out[b] = 0;
+        }
+        return;
+    }
+    // 2: starting slots
+    int n0 = 0;
+    if (init_palette) {
+        n0 = init_sizes[b];
+        n0 = n0 < 0 ? 0 : (n0 > K ? K : n0);
+    }
+    int n;
+    if (n0 > 0) {                                          // the whole workgroup
+        n = n0 < colours ? n0 : colours;
+        for (int k = tid; k < n; k += PAL_THREADS) {
+            const int4 c = *(const int4*)(init_palette + ((long long)b * K + k) * 4);
+            s->slot[k] = pal_snap_slot(((unsigned)c.x & 255u) | (((unsigned)c.y & 255u) << 8) | (((unsigned)c.z & 255u) << 16) |
+                                           (((unsigned)c.w & 255u) << 24), k);
+        }
+    } else {
+        n = colours;
+        unsigned c = 0u, cc = 0u;                          // the slot chosen last, in every lane's registers
+        for (int j = 0; j < n; ++j) {
+            unsigned long long best = 0ull;
+            for (int p = tid; p < HW; p += PAL_THREADS) {
+                const unsigned q = keys[p];
+                unsigned m = far[p];
+                if (j > 0) {
+                    const unsigned d = __builtin_amdgcn_udot4(q, q, 0u, false) + cc - 2u * __builtin_amdgcn_udot4(q, c, 0u, false);
+                    m = d < m ? d : m;
+                    far[p] = m;
+                }
+                const unsigned long long cand = ((unsigned long long)m << 32) | (unsigned long long)(~q);
+                best = cand > best ? cand : best;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(best, o, 64);
+                best = other > best ? other : best;
+            }
+            if (lane == 0) s->red[j & 1][wave] = best;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < PAL_THREADS / 64; ++w) best = s->red[j & 1][w] > best ? s->red[j & 1][w] : best;
+            c = ~(unsigned)best;
+            cc = __builtin_amdgcn_udot4(c, c, 0u, false);
+            if (tid == 0) s->slot[j] = pal_snap_slot(c, j);
+        }
+    }
+    for (int k = tid; k < n; k += PAL_THREADS)
+#pragma unroll
+        for (int a = 0; a < 5; ++a) s->acc[a][k] = 0u;
+    __syncthreads();
+    // 3: Lloyd passes
+    int iters = 0;
+    for (int t = 1; t <= iterations; ++t) {
+        for (int p0 = 0; p0 < HW; p0 += PAL_THREADS * PAL_SNAP_PIX) {
+            unsigned q[PAL_SNAP_PIX], key[PAL_SNAP_PIX];
+            bool valid[PAL_SNAP_PIX];
+#pragma unroll
+            for (int j = 0; j < PAL_SNAP_PIX; ++j) {
+                const int p = p0 + j * PAL_THREADS + tid;
+                valid[j] = p < HW;
+                q[j] = valid[j] ? keys[p] : 0u;
+                key[j] = 0xFFFFFFFFu;
+            }
+#pragma unroll 4
+            for (int k = 0; k < n; ++k) {
+                const uint2 sl = s->slot[k];               // wave-uniform address: one broadcast read for the lane's pixels
+#pragma unroll
+                for (int j = 0; j < PAL_SNAP_PIX; ++j) key[j] = pal_snap_min(key[j], q[j], sl);
+            }
+#pragma unroll
+            for (int j = 0; j < PAL_SNAP_PIX; ++j) pal_q_add(s->acc, valid[j], key[j] & 255u, q[j]);
+        }
+        __syncthreads();
+        if (tid < n) {                                     // n <= PAL_MAX = PAL_THREADS: one lane per slot
+            const unsigned cnt = s->acc[0][tid];
+            if (cnt) {                                     // floor((2 S + n_k) / (2 n_k)); a slot without pixels keeps its colour
+                unsigned pk = 0u;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) pk |= ((2u * s->acc[1 + a][tid] + cnt) / (2u * cnt)) << (8 * a);
+                if (pk != s->slot[tid].x) {
+                    s->slot[tid] = pal_snap_slot(pk, tid);
+                    s->changed[t & 1] = 1;
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 5; ++a) s->acc[a][tid] = 0u;
+        }
+        if (tid == 0) s->changed[(t + 1) & 1] = 0;         // read by every lane before the barrier above, raised after the next one
+        __syncthreads();
+        iters = t;
+        if (!s->changed[t & 1]) break;                     // the whole workgroup
+    }
+    // 4: the distinct colours of the slots in ascending key order
+    unsigned key = 0u;
+    if (tid < n) {
+        key = s->slot[tid].x;
+        unsigned f = 1u;
+        for (int j = 0; j < tid; ++j) f = s->slot[j].x == key ? 0u : f;
+        s->first[tid] = f;
+    }
+    __syncthreads();
+    int size = 0, rank = 0;
+    for (int j = 0; j < n; ++j) {
+        const int f = (int)s->first[j];
+        size += f;
+        rank += (f && s->slot[j].x < key) ? 1 : 0;
+    }
+    if (tid < n && s->first[tid])
+        *(int4*)(row + 4 * rank) = make_int4((int)(key & 255u), (int)((key >> 8) & 255u), (int)((key >> 16) & 255u), (int)(key >> 24));
+    for (int i = size + tid; i < K; i += PAL_THREADS) *(int4*)(row + 4 * i) = make_int4(0, 0, 0, 0);
+    if (tid == 0) {
+        sizes_out[b] = size;
+        if (iters_out) iters_out[b] = iters;
+    }
 }
 
 // Differentiable palette projection (DESIGN.md "palette projection"): every pixel replaced by a colour of its image's palette, on the
@@ -713,6 +953,26 @@ extern "C" int p2p_palette_snap(int N, int H, int W, const float* img, const int
     palette_snap_kernel<<<dim3(pal_chunks(H, W, PAL_SNAP_PIX), N), PAL_THREADS, 0, st>>>(H * W, img, palette, sizes, K, index_out, image_out,
                                                                                           dist_out, counts_out, stats_out);
     return p2p_check_launch("p2p_palette_snap");
+}
+
+extern "C" int p2p_palette_quantize(int N, int H, int W, const float* img, int colours, int iterations, const int* init_palette,
+                                    const int* init_sizes, int K, int* palette_out, int* sizes_out, int* iters_out, void* stream) {
+    P2P_REQUIRE(N > 0 && H > 0 && W > 0, "p2p_palette_quantize: bad shape %d x %d x %d", N, H, W);
+    P2P_REQUIRE((long long)H * W <= PAL_Q_MAXPIX, "p2p_palette_quantize: %d x %d pixels, an image has at most 2^14 (128 x 128): its keys stay in LDS",
+                H, W);
+    P2P_REQUIRE(K >= 1 && K <= PAL_MAX, "p2p_palette_quantize: K = %d, a palette has 1..%d slots", K, PAL_MAX);
+    P2P_REQUIRE(colours >= 1 && colours <= K, "p2p_palette_quantize: colours = %d, expected 1..K = %d", colours, K);
+    P2P_REQUIRE(iterations >= 0 && iterations <= 64, "p2p_palette_quantize: iterations = %d, expected 0..64", iterations);
+    P2P_REQUIRE((init_palette == nullptr) == (init_sizes == nullptr), "p2p_palette_quantize: init_palette and init_sizes are given together or not at all");
+    P2P_REQUIRE(img && palette_out && sizes_out, "p2p_palette_quantize: null pointer");
+    P2P_REQUIRE(((uintptr_t)img % 16) == 0 && ((uintptr_t)palette_out % 16) == 0 && ((uintptr_t)init_palette % 16) == 0,
+                "p2p_palette_quantize: img, palette_out and init_palette must be 16-byte aligned");
+    const int lds = (int)sizeof(PalQuantScratch) + 8 * H * W;
+    static bool attr_done = false;
+    if (!attr_done) attr_done = p2p_allow_lds((const void*)palette_quantize_kernel, 160 * 1024, "palette_quantize_kernel");
+    palette_quantize_kernel<<<N, PAL_THREADS, lds, (hipStream_t)stream>>>(H * W, img, colours, iterations, init_palette, init_sizes, K, palette_out,
+                                                                          sizes_out, iters_out);
+    return p2p_check_launch("p2p_palette_quantize");
 }
 
 extern "C" int p2p_palette_project_fwd(int N, int H, int W, const float* img, const int* palette, const int* sizes, int K, float tau, int hard,

@@ -75,6 +75,7 @@ constexpr Entry TABLE[] = {
     P2P_E(p2p_soft_palette_tv_bwd) P2P_E(p2p_palette_loss) P2P_E(p2p_finish_losses2)
     P2P_E(p2p_palette_lookup_fwd) P2P_E(p2p_palette_lookup_bwd)
     P2P_E(p2p_adam_tick_sched) P2P_E(p2p_sumsq_partials) P2P_E(p2p_clip_scale) P2P_E(p2p_adam_step)
+    P2P_E(p2p_palette_quantize)
 };
 #undef P2P_E
 constexpr int NFN = (int)(sizeof(TABLE) / sizeof(TABLE[0]));

@@ -14,7 +14,10 @@ Jacobian of the soft projection, or the straight-through identity), so a tape st
 (Pix2PixPaletteSnapModel).  `palette_lookup` serves the palette-index model instead: it maps (B, H, W, 256)
 probabilities over a palette's slots to the RGBA image they stand for (p2p_palette_lookup_fwd / _bwd: the expected colour, or the
 argmax's colour with the straight-through gradient), so image-space losses reach the indexed generator (Pix2PixIndexedColourModel;
-DESIGN.md 6g).  All kernels launch on the current stream; there is no CPU path.
+DESIGN.md 6g).  `quantize_palette` / `quantize` need no palette from elsewhere: they derive one of at most K colours from the image itself
+(p2p_palette_quantize: farthest-point starting slots and Lloyd passes in exact integer arithmetic) and snap to it --
+the last step of inference (Pix2PixModel.generate(snap=K), S2SModel.report_quantized).  All kernels launch on the current stream;
+there is no CPU path.
 
 The default temperature 1e-3 makes a pixel that sits on a palette colour count for that slot alone (two colours one 8-bit step apart
 in one channel are 1.5e-5 apart in d, a weight ratio of 0.985; a pixel half-way between two clearly different colours is shared).
@@ -309,6 +312,73 @@ def snap_to_palette(image_batch, palette, sizes=None, device=None):
         L.call("p2p_palette_snap", B, H, W, _p(img), _p(pal), _p(sz), K, _p(index), _p(image), _p(distance), _p(counts), _p(stats),
                _stream(dev))
     return PaletteSnap(index, image, distance, counts, stats[:, 0], stats[:, 1])
+
+
+MAX_QUANTIZE_PIXELS = 1 << 14          # p2p_palette_quantize keeps an image's keys in LDS: 128 x 128 at most
+MAX_QUANTIZE_ITERATIONS = 64
+
+
+def _checked_quantize_args(images, colours, iterations, init):
+    """everything quantize_palette can refuse without a device: raises ValueError"""
+    if isinstance(colours, bool) or not isinstance(colours, int) or not 1 <= colours <= MAX_PALETTE_SIZE:
+        raise ValueError(f"colours is an int in 1..{MAX_PALETTE_SIZE}, got {colours!r}")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= MAX_QUANTIZE_ITERATIONS:
+        raise ValueError(f"iterations is an int in 0..{MAX_QUANTIZE_ITERATIONS}, got {iterations!r}")
+    shape = tuple(int(x) for x in (images if hasattr(images, "shape") else torch.as_tensor(images)).shape)
+    if len(shape) != 4 or shape[3] != 4 or 0 in shape:
+        raise ValueError(f"expected a non-empty (B, H, W, 4) RGBA batch, got {shape}")
+    if shape[1] * shape[2] > MAX_QUANTIZE_PIXELS:
+        raise ValueError(f"{shape[1]} x {shape[2]} pixels: quantize_palette takes images of at most {MAX_QUANTIZE_PIXELS} pixels (128 x 128)")
+    if init is None:
+        return None
+    try:
+        pal, sizes = init
+    except (TypeError, ValueError):
+        raise ValueError("init is None or a (palette (B, K, 4), sizes (B,) or None) pair") from None
+    pal = _checked_palette(pal, shape[0])
+    if sizes is not None and tuple(torch.as_tensor(sizes).shape) != (shape[0],):
+        raise ValueError(f"expected {shape[0]} palette sizes, got shape {tuple(torch.as_tensor(sizes).shape)}")
+    return pal, sizes
+
+
+def quantize_palette(images, colours=16, iterations=8, init=None, device=None):
+    """A palette of at most `colours` colours for every image of a (B, H, W, 4) batch in [-1, 1], derived from the image itself
+    (p2p_palette_quantize): (palette int32 (B, 256, 4), sizes int32 (B,)) on the device, in extract_palette_batch's
+    format -- sizes[b] distinct 0..255 RGBA rows in ascending order of r + 256 g + 65536 b + 2^24 a, then zero rows.  An image with
+    at most `colours` distinct 8-bit colours gets exactly those.  Otherwise an integer k-means: `colours` starting slots by
+    farthest-point selection from the image's lowest key (or the first min(sizes, colours) rows of `init`, a (palette (B, K <= 256,
+    4), sizes (B,) or None) pair as generate(snap=) takes it; an image whose size is <= 0 starts from the farthest points), then up
+    to `iterations` (0..64) Lloyd passes with snap_to_palette's nearest-slot rule and centroids rounded half up, stopping at a fixed
+    point.  Rounded centroids can coincide: sizes[b] <= colours.  Exact integer arithmetic: the result depends only on the image's
+    multiset of quantised colours.  H * W <= 2^14 (128 x 128).  NOT differentiable; no host sync."""
+    checked = _checked_quantize_args(images, colours, iterations, init)
+    L.lib()          # fail loudly if the HIP library is missing: there is no CPU path
+    dev = _device_of(images, device)
+    img = _rgba(images, dev).detach()
+    B, H, W, _ = (int(x) for x in img.shape)
+    K = MAX_PALETTE_SIZE
+    palette = torch.empty((B, K, 4), dtype=torch.int32, device=dev)
+    sizes = torch.empty((B,), dtype=torch.int32, device=dev)
+    init_pal = init_sz = C.c_void_p(0)
+    if checked is not None:
+        pal, sz = _palette_args(checked[0], checked[1], B, dev)
+        padded = torch.zeros((B, K, 4), dtype=torch.int32, device=dev)
+        padded[:, :pal.shape[1]] = pal
+        sz = sz.clamp(max=int(pal.shape[1]))          # rows past the given K are padding, not slots
+        init_pal, init_sz = _p(padded), _p(sz)
+    with torch.cuda.device(dev):
+        L.call("p2p_palette_quantize", B, H, W, _p(img), colours, iterations, init_pal, init_sz, K, _p(palette), _p(sizes), C.c_void_p(0),
+               _stream(dev))
+    return palette, sizes
+
+
+def quantize(images, colours=16, iterations=8, init=None, device=None):
+    """quantize_palette followed by snap_to_palette: (PaletteSnap, palette, sizes).  PaletteSnap.image is the batch with every image
+    reduced to at most `colours` colours of its own (an image that had no more keeps its colours bit for bit after 8-bit rounding),
+    .index with the palette is the indexed form (io_utils.indexed_to_rgba, PNG), .distance_sum the quantisation error."""
+    dev = _device_of(images, device)
+    palette, sizes = quantize_palette(images, colours, iterations, init, device=dev)
+    return snap_to_palette(images, palette, sizes, device=dev), palette, sizes
 
 
 def palette_metrics(fake_images, real_images, device=None):

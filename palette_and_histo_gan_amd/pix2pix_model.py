@@ -318,12 +318,18 @@ class Pix2PixModel(S2SModel):
         one (False).  `snap` (build-added) moves every generated pixel to the nearest colour of a palette
         (palette.snap_to_palette, f32 result, not differentiable): "target" / "source" use the palette extracted from that image
         of the batch on the device (an image with more than MAX_PALETTE_SIZE colours is returned as generated), a
-        (palette (B, K, 4), sizes (B,) or None) pair is used as given; None returns the generator's output unchanged."""
+        (palette (B, K, 4), sizes (B,) or None) pair is used as given; an int K in 1..256 needs no palette from elsewhere: every
+        generated image is reduced to at most K colours of its own (palette.quantize: integer k-means on the image, then the snap;
+        sprites of at most 128 x 128); None returns the generator's output unchanged."""
+        if isinstance(snap, bool):
+            raise TypeError(f'snap is None, "target", "source", a number of colours or a (palette, sizes) pair, got {snap!r}')
         source_image, target_image = batch
         with self._weights_for(averaged):
             fake_image = self.generator(source_image, training=True)
         if snap is None:
             return fake_image
+        if isinstance(snap, int):
+            return _palette.quantize(fake_image, colours=snap, device=fake_image.device)[0].image
         if isinstance(snap, str):
             if snap not in ("target", "source"):
                 raise ValueError(f'snap is None, "target", "source" or a (palette, sizes) pair, got {snap!r}')

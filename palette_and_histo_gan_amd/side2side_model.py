@@ -269,6 +269,13 @@ class S2SModel(ABC):
                         p_train, p_test = self.report_palette(step=(step + 1) // update_steps)
                         print(f" Palette: off {p_train['off_palette']:.5f} / {p_test['off_palette']:.5f}, "
                               f"tv {p_train['histogram_tv']:.5f} / {p_test['histogram_tv']:.5f} (train/test)")
+                if "evaluate_quantized" in callbacks:
+                    if self._has_indexed_batches():
+                        print(" Quantized: skipped (the indexed model is on-palette by construction)")
+                    else:
+                        q_train, q_test = self.report_quantized(step=(step + 1) // update_steps)
+                        print(f" Quantized: L1 {q_train['l1_quantized']:.5f} / {q_test['l1_quantized']:.5f}, "
+                              f"rms {q_train['rms_distance']:.5f} / {q_test['rms_distance']:.5f} (train/test)")
                 if "evaluate_fid" in callbacks:
                     from . import frechet_inception_distance as fid
                     if fid.configured_weights() is None:
@@ -462,6 +469,35 @@ class S2SModel(ABC):
             self.summary_writer.scalar("palette-off/test", test_value["off_palette"], step)
             self.summary_writer.scalar("palette-tv/train", train_value["histogram_tv"], step)
             self.summary_writer.scalar("palette-tv/test", test_value["histogram_tv"], step)
+        return train_value, test_value
+
+    def evaluate_quantized(self, real_images, fake_images, colours=16):
+        """build-added: what reducing every generated image to at most `colours` colours of its own costs (palette.quantize,
+        DESIGN.md 6i).  A dict of floats: l1 (evaluate_l1 of the generated images), l1_quantized (the same of the quantised ones),
+        rms_distance (sqrt(distance_sum / (4 HW)) / 255 of the quantising snap, mean over the images) and colours (mean palette size)"""
+        from . import palette
+        fake = torch.as_tensor(fake_images, dtype=torch.float32)
+        snap, _, sizes = palette.quantize(fake, colours=colours, device=getattr(getattr(self, "engine", None), "device", None))
+        hw = float(fake.shape[1] * fake.shape[2])
+        rms = (torch.sqrt(snap.distance_sum.to(torch.float64) / (hw * 4.0)) / 255.0).mean()
+        return {"l1": float(self.evaluate_l1(real_images, fake)), "l1_quantized": float(self.evaluate_l1(real_images, snap.image.cpu())),
+                "rms_distance": float(rms), "colours": float(sizes.to(torch.float64).mean())}
+
+    def report_quantized(self, num_images=TEST_SIZE, colours=16, step=None):
+        """build-added, beside report_l1 and over the same samples: the L1 distance to the targets before and after every generated
+        image is quantised to at most `colours` colours of its own -- the inference path generate(snap=colours) -- with the
+        quantisation error and the palette sizes (evaluate_quantized).  Returns (train, test) dicts."""
+        if self._has_indexed_batches():
+            raise NotImplementedError("on-palette by construction")
+        train_real_images, train_fake_images = self.select_examples_for_evaluation(num_images, self.train_ds)
+        test_real_images, test_fake_images = self.select_examples_for_evaluation(num_images, self.test_ds)
+        train_value = self.evaluate_quantized(train_real_images, train_fake_images, colours)
+        test_value = self.evaluate_quantized(test_real_images, test_fake_images, colours)
+        if self.summary_writer is not None and step is not None:
+            self.summary_writer.scalar("quantized-l1/train", train_value["l1_quantized"], step)
+            self.summary_writer.scalar("quantized-l1/test", test_value["l1_quantized"], step)
+            self.summary_writer.scalar("quantized-rms/train", train_value["rms_distance"], step)
+            self.summary_writer.scalar("quantized-rms/test", test_value["rms_distance"], step)
         return train_value, test_value
 
     def report_l1(self, num_images=TEST_SIZE, step=None):
