@@ -87,9 +87,11 @@ def test_vjp_at_general_arguments_matches_the_f64_oracle(size, method, sigma):
 
 @pytest.mark.parametrize("size,method,sigma", [(64, "inverse-quadratic", 0.02), (32, "RBF", 0.1)])
 def test_vjp_of_three_channel_and_non_square_images(size, method, sigma):
-    """a 3-channel input (view ld = 3) and a 40 x 24 image (tail pixel batches), both backward paths"""
+    """a 3-channel input (view ld = 3), a 40 x 24 image (non-square, but 960 = 10 x 96 = 15 x 64 = 30 x 32 pixels: a whole number
+    of batches in every kernel) and a 40 x 25 one (1000 = 10 x 96 + 40 = 15 x 64 + 40 = 31 x 32 + 8: a partial last batch in each),
+    both backward paths; tests/test_hist_shapes_gpu.py goes through the tails class by class"""
     kw = dict(size=size, method=method, sigma=sigma)
-    for img in (mid_range(47, 2, 64, 64, ch=3), mid_range(48, 2, 40, 24)):
+    for img in (mid_range(47, 2, 64, 64, ch=3), mid_range(48, 2, 40, 24), mid_range(58, 2, 40, 25)):
         g = upstream(49, 2, size)
         got = vjp(lambda x: H.calculate_rgbuv_histogram(x, **kw), img, g)
         assert got.shape == img.shape
