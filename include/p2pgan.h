@@ -736,8 +736,9 @@ int p2p_clip_scale(const float* const* partials, const int* nparts, int nbuf, fl
  * _excl do (e null: no moving average; ex_lo == ex_hi: no hole), plus
  *   gscale_dev   device scalar the gradient is multiplied by (p2p_clip_scale's; null: 1)
  *   clipvalue    hyper->clipvalue > 0: g = fminf(fmaxf(g, -c), c) before everything else (<= 0: off)
- * Both are HOST structs read when the call is issued; `hyper` is shared by every launch of one optimizer.  The element goes
- * through the same update as the four entry points: with both options off the results are theirs bit for bit. */
+ * Both are HOST structs read when the call is issued; `hyper` is shared by every launch of one optimizer.  The five entry points
+ * are one kernel behind one launcher (csrc/optim.hip adam_kernel, adam_launch): with both options off this call runs the very
+ * code of the entry point it stands for, and with them on the element still goes through the same update. */
 typedef struct p2p_adam_hyper {
     float beta1, beta2, eps, clipvalue, ema_decay;
 } p2p_adam_hyper;

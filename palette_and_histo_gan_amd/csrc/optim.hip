@@ -41,9 +41,9 @@ __global__ void adam_tick_kernel(int* __restrict__ t, float* __restrict__ lr_t, 
 }
 
 // One element of the Keras Adam step with its roundings spelled out: m' = fma(1 - b1, g, b1 * m), v' = fma(b2, v, ((1 - b2) * g) * g).
-// That is what the compiler's contraction made of the vector loop of adam_flat_dev_kernel; left to the compiler, a scalar copy of
+// That is what the compiler's contraction made of the vector loop of the first flat kernel; left to the compiler, a scalar copy of
 // the same expressions (a tail, a vector cut by an excluded range) came out with other fusions and other last bits.  Every path
-// of adam_flat_dev_kernel and adam_flat_dev_excl_kernel goes through here: they agree bit for bit by construction.
+// of adam_kernel goes through here, so the five entry points it serves agree bit for bit by construction.
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
                                             float gscale) {
 #pragma clang fp contract(off)
@@ -56,7 +56,7 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
 // Exponential moving average of the generator's masters: e' = e + (1 - beta_t) * (p' - e) with
 // beta_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay and t = the Adam iteration p2p_adam_tick left in t_dev.  Three correctly
 // rounded f32 operations per element and no contraction: a NumPy float32 restatement gives the same bits, and p' == e leaves e
-// as it is.  Every path of the three kernels that average (vector body, straddling vectors, tails) goes through here.
+// as it is.  Every path of the two kernels that average (vector body, straddling vectors, tails) goes through here.
 struct EmaArgs { float* e; const int* t_dev; float decay; int warmup; };
 
 __device__ __forceinline__ float ema_one_minus_beta(const EmaArgs& a) {
@@ -76,41 +76,123 @@ __device__ __forceinline__ void ema_update(float& e, float p, float omb) {
     e = e + s;
 }
 
-template <bool EMA>
-__global__ void adam_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                     float* __restrict__ v, long long n, const float* __restrict__ lr_t_dev, float b1,
-                                     float b2, float eps, float gscale, EmaArgs ema) {
-    const float lr_t = lr_t_dev[0];
-    float omb = 0.f;
-    if constexpr (EMA) omb = ema_one_minus_beta(ema);
-    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    long long stride = (long long)gridDim.x * blockDim.x * 4;
-    for (; i + 3 < n; i += stride) {
-        f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
+// The gradient options of p2p_adam_step, in front of adam_update: the clamp first, then the device scale.
+// Both are exact no-ops when off (g * 1.0f == g).
+struct GradOpts { const float* gscale_dev; float clipvalue; };
+
+__device__ __forceinline__ float grad_clamp(float g, float c) { return c > 0.f ? fminf(fmaxf(g, -c), c) : g; }
+
+// What one launch holds fixed for every element.
+struct AdamCoef { float lr_t, b1, b2, eps, gscale, clip, omb; };
+
+// The live element j, and the whole 16-byte vector at i: the only two places of the flat pass that touch an element.
+template <bool EMA, bool OPTS>
+__device__ __forceinline__ void adam_element(float* p, const float* g, float* m, float* v, float* e, long long j,
+                                             const AdamCoef& c) {
+    adam_update(p[j], OPTS ? grad_clamp(g[j], c.clip) : g[j], m[j], v[j], c.lr_t, c.b1, c.b2, c.eps, c.gscale);
+    if constexpr (EMA) ema_update(e[j], p[j], c.omb);
+}
+
+template <bool EMA, bool OPTS>
+__device__ __forceinline__ void adam_vector(float* p, const float* g, float* m, float* v, float* e, long long i,
+                                            const AdamCoef& c) {
+    f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float pk = pi[k], mk = mi[k], vk = vi[k];
+        adam_update(pk, OPTS ? grad_clamp(gi[k], c.clip) : gi[k], mk, vk, c.lr_t, c.b1, c.b2, c.eps, c.gscale);
+        pi[k] = pk; mi[k] = mk; vi[k] = vk;
+    }
+    *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
+    if constexpr (EMA) {
+        f32x4 ei = *(const f32x4*)(e + i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float pk = pi[k], mk = mi[k], vk = vi[k];
-            adam_update(pk, gi[k], mk, vk, lr_t, b1, b2, eps, gscale);
-            pi[k] = pk; mi[k] = mk; vi[k] = vk;
+            float ek = ei[k];
+            ema_update(ek, pi[k], c.omb);
+            ei[k] = ek;
         }
-        *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
-        if constexpr (EMA) {
-            f32x4 ei = *(const f32x4*)(ema.e + i);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float ek = ei[k];
-                ema_update(ek, pi[k], omb);
-                ei[k] = ek;
-            }
-            *(f32x4*)(ema.e + i) = ei;
+        *(f32x4*)(e + i) = ei;
+    }
+}
+
+// The flat Adam pass behind p2p_adam_flat_dev, _excl, p2p_adam_ema_flat_dev, _excl and p2p_adam_step.
+//   HOLE  elements [ex_lo, ex_hi) are neither read nor written.  The 16-byte vectors that lie wholly inside the hole are taken out
+//         of the index space (every lane keeps a whole share of live vectors); a vector that straddles an end of the hole is
+//         updated element by element.  HOLE = false is the plain index space and its register footprint: the early Adam over
+//         the generator's head buckets runs beside the weight-gradient stream's last kernels and must leave them room.
+//   EMA   the moving average of the live elements in the same pass (e has the hole too): the fresh p is still in registers, so
+//         the average costs one read and one write of e (8 bytes per element) and no launch.
+//   OPTS  the gradient options, read from `o`; without them `gscale` is the by-value scale of the flat entry points and no
+//         instruction of the options is compiled in (the option-carrying form costs the batch-256 step
+//         time that its arithmetic does not explain, so the default step does not run it).
+template <bool EMA, bool HOLE, bool OPTS>
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            long long n, long long ex_lo, long long ex_hi, const float* __restrict__ lr_t_dev, float b1, float b2,
+                            float eps, float gscale, GradOpts o, EmaArgs ema) {
+    AdamCoef c = {lr_t_dev[0], b1, b2, eps, gscale, 0.f, 0.f};
+    if constexpr (OPTS) {
+        c.gscale = o.gscale_dev ? o.gscale_dev[0] : 1.0f;
+        c.clip = o.clipvalue;
+    }
+    if constexpr (EMA) c.omb = ema_one_minus_beta(ema);
+    const long long hv_lo = HOLE ? (ex_lo + 3) / 4 : 0, hv_hi = HOLE ? ex_hi / 4 : 0;
+    const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
+    const long long live = n / 4 - hole;
+    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if constexpr (!HOLE && !OPTS) {
+        // the vectors the loop below visits with an empty hole.  The default step runs this form beside the weight-gradient
+        // stream, and its timings were taken with this loop's code: kept apart from the optioned one
+        for (long long i = q * 4; i + 3 < n; i += stride * 4) adam_vector<EMA, OPTS>(p, g, m, v, ema.e, i, c);
+    } else {
+        for (; q < live; q += stride) {
+            const long long i = (!HOLE || q < hv_lo ? q : q + hole) * 4;
+            if (!HOLE || i + 4 <= ex_lo || i >= ex_hi) adam_vector<EMA, OPTS>(p, g, m, v, ema.e, i, c);
+            else
+                for (long long j = i; j < i + 4; ++j)
+                    if (j < ex_lo || j >= ex_hi) adam_element<EMA, OPTS>(p, g, m, v, ema.e, j, c);
         }
     }
     // tail (n is padded to a multiple of 4 by the host layout, kept for safety)
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long j = n / 4 * 4; j < n; ++j) {
-            adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
-            if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
-        }
+        for (long long j = n / 4 * 4; j < n; ++j)
+            if (!HOLE || j < ex_lo || j >= ex_hi) adam_element<EMA, OPTS>(p, g, m, v, ema.e, j, c);
+}
+
+// Grid of a pass in which thread q takes the 16-byte vectors q, q + grid * 256, ...: one thread per vector up to 8192 workgroups.
+static inline dim3 vector_grid(long long nvec) {
+    const long long blocks = (nvec + 255) / 256;
+    return dim3((unsigned)(blocks > 8192 ? 8192 : blocks < 1 ? 1 : blocks));
+}
+
+template <typename... P>
+static inline bool aligned16(const P*... ptrs) {
+    return ((((uintptr_t)ptrs) | ...) % 16) == 0;
+}
+
+// Every check, the grid and the choice of instantiation for the five entry points; `who` names the one that was called.
+// `gscale` is the by-value scale of the four flat entry points.  OPTS only where an option is on: p2p_adam_step with both off
+// runs the code of the flat entry points.
+static int adam_launch(const p2p_adam_args& a, const p2p_adam_hyper& h, float gscale, bool ema, const char* who, void* stream) {
+    P2P_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0 && a.lr_t_dev, "%s: bad args", who);
+    P2P_REQUIRE(!ema || (a.e && a.t_dev), "%s: the moving average needs e and t_dev", who);
+    P2P_REQUIRE(0 <= a.ex_lo && a.ex_lo <= a.ex_hi && a.ex_hi <= a.n, "%s: the excluded range must lie inside [0, n)", who);
+    P2P_REQUIRE(aligned16(a.p, a.g, a.m, a.v, a.e), "%s: buffers must be 16-byte aligned", who);
+    const long long hv_lo = (a.ex_lo + 3) / 4, hv_hi = a.ex_hi / 4;
+    const long long live = a.n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
+    const dim3 grid = vector_grid(live);
+    const GradOpts o = {a.gscale_dev, h.clipvalue};
+    const EmaArgs avg = ema ? EmaArgs{a.e, a.t_dev, h.ema_decay, a.ema_warmup} : EmaArgs{nullptr, nullptr, 0.f, 0};
+    const bool hole = a.ex_hi > a.ex_lo, opts = a.gscale_dev || h.clipvalue > 0.f;
+#define ADAM_CASE(EMA, HOLE, OPTS)                                                                                                \
+    if (ema == EMA && hole == HOLE && opts == OPTS)                                                                                \
+        adam_kernel<EMA, HOLE, OPTS><<<grid, 256, 0, (hipStream_t)stream>>>(a.p, a.g, a.m, a.v, a.n, a.ex_lo, a.ex_hi, a.lr_t_dev, \
+                                                                          h.beta1, h.beta2, h.eps, gscale, o, avg)
+    ADAM_CASE(false, false, false); ADAM_CASE(true, false, false); ADAM_CASE(false, true, false); ADAM_CASE(true, true, false);
+    ADAM_CASE(false, false, true);  ADAM_CASE(true, false, true);  ADAM_CASE(false, true, true);  ADAM_CASE(true, true, true);
+#undef ADAM_CASE
+    return p2p_check_launch(who);
 }
 
 extern "C" int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1, float beta2, void* stream) {
@@ -121,120 +203,28 @@ extern "C" int p2p_adam_tick(int* t_dev, float* lr_t_dev, float lr, float beta1,
 
 extern "C" int p2p_adam_flat_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_t_dev,
                                  float beta1, float beta2, float eps, float gscale, void* stream) {
-    P2P_REQUIRE(p && g && m && v && n > 0 && lr_t_dev, "p2p_adam_flat_dev: bad args");
-    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-                "p2p_adam_flat_dev: buffers must be 16-byte aligned");
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    adam_flat_dev_kernel<false><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps,
-                                                                                        gscale, EmaArgs{nullptr, nullptr, 0.f, 0});
-    return p2p_check_launch("p2p_adam_flat_dev");
+    const p2p_adam_args a = {p, g, m, v, nullptr, n, 0, 0, lr_t_dev, nullptr, nullptr, nullptr, 0, 0};
+    return adam_launch(a, {beta1, beta2, eps, 0.f, 0.f}, gscale, false, "p2p_adam_flat_dev", stream);
 }
 
-// p2p_adam_flat_dev and the moving average of the same element in the same pass: the fresh p is still in registers, so the average
-// costs one read and one write of e (8 bytes per element) and no launch.  p, m, v: the instructions of p2p_adam_flat_dev.
 extern "C" int p2p_adam_ema_flat_dev(float* p, const float* g, float* m, float* v, float* e, long long n, const float* lr_t_dev,
                                      float beta1, float beta2, float eps, float gscale, const int* t_dev, float decay, int warmup,
                                      void* stream) {
-    P2P_REQUIRE(p && g && m && v && e && n > 0 && lr_t_dev && t_dev, "p2p_adam_ema_flat_dev: bad args");
-    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                    ((uintptr_t)e % 16) == 0,
-                "p2p_adam_ema_flat_dev: buffers must be 16-byte aligned");
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    adam_flat_dev_kernel<true><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t_dev, beta1, beta2, eps,
-                                                                                       gscale, EmaArgs{e, t_dev, decay, warmup});
-    return p2p_check_launch("p2p_adam_ema_flat_dev");
-}
-
-// adam_flat_dev_kernel with a hole: elements [ex_lo, ex_hi) are neither read nor written.  The 16-byte vectors that lie wholly
-// inside the hole are taken out of the index space (every lane keeps a whole share of live vectors); a vector that straddles an
-// end of the hole is updated element by element.  The arithmetic is adam_update's, as in adam_flat_dev_kernel: bit-identical
-// outside the hole.  EMA: the moving average of the live elements in the same pass (e has the hole too).
-template <bool EMA>
-__global__ void adam_flat_dev_excl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, long long n, long long ex_lo, long long ex_hi,
-                                          const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale,
-                                          EmaArgs ema) {
-    const float lr_t = lr_t_dev[0];
-    float omb = 0.f;
-    if constexpr (EMA) omb = ema_one_minus_beta(ema);
-    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
-    const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
-    const long long live = n / 4 - hole;
-    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; q < live; q += stride) {
-        const long long i = (q < hv_lo ? q : q + hole) * 4;
-        if (i + 4 <= ex_lo || i >= ex_hi) {
-            f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float pk = pi[k], mk = mi[k], vk = vi[k];
-                adam_update(pk, gi[k], mk, vk, lr_t, b1, b2, eps, gscale);
-                pi[k] = pk; mi[k] = mk; vi[k] = vk;
-            }
-            *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
-            if constexpr (EMA) {
-                f32x4 ei = *(const f32x4*)(ema.e + i);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float ek = ei[k];
-                    ema_update(ek, pi[k], omb);
-                    ei[k] = ek;
-                }
-                *(f32x4*)(ema.e + i) = ei;
-            }
-        } else {
-            for (long long j = i; j < i + 4; ++j)
-                if (j < ex_lo || j >= ex_hi) {
-                    adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
-                    if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
-                }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long j = n / 4 * 4; j < n; ++j)
-            if (j < ex_lo || j >= ex_hi) {
-                adam_update(p[j], g[j], m[j], v[j], lr_t, b1, b2, eps, gscale);
-                if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
-            }
+    const p2p_adam_args a = {p, g, m, v, e, n, 0, 0, lr_t_dev, nullptr, t_dev, nullptr, warmup, 0};
+    return adam_launch(a, {beta1, beta2, eps, 0.f, decay}, gscale, true, "p2p_adam_ema_flat_dev", stream);
 }
 
 extern "C" int p2p_adam_flat_dev_excl(float* p, const float* g, float* m, float* v, long long n, long long ex_lo, long long ex_hi,
                                       const float* lr_t_dev, float beta1, float beta2, float eps, float gscale, void* stream) {
-    P2P_REQUIRE(p && g && m && v && n > 0 && lr_t_dev, "p2p_adam_flat_dev_excl: bad args");
-    P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_adam_flat_dev_excl: the excluded range must lie inside [0, n)");
-    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-                "p2p_adam_flat_dev_excl: buffers must be 16-byte aligned");
-    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
-    const long long live = n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
-    long long blocks = (live + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    adam_flat_dev_excl_kernel<false><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(
-        p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1, beta2, eps, gscale, EmaArgs{nullptr, nullptr, 0.f, 0});
-    return p2p_check_launch("p2p_adam_flat_dev_excl");
+    const p2p_adam_args a = {p, g, m, v, nullptr, n, ex_lo, ex_hi, lr_t_dev, nullptr, nullptr, nullptr, 0, 0};
+    return adam_launch(a, {beta1, beta2, eps, 0.f, 0.f}, gscale, false, "p2p_adam_flat_dev_excl", stream);
 }
 
 extern "C" int p2p_adam_ema_flat_dev_excl(float* p, const float* g, float* m, float* v, float* e, long long n, long long ex_lo,
                                           long long ex_hi, const float* lr_t_dev, float beta1, float beta2, float eps, float gscale,
                                           const int* t_dev, float decay, int warmup, void* stream) {
-    P2P_REQUIRE(p && g && m && v && e && n > 0 && lr_t_dev && t_dev, "p2p_adam_ema_flat_dev_excl: bad args");
-    P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_adam_ema_flat_dev_excl: the excluded range must lie inside [0, n)");
-    P2P_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                    ((uintptr_t)e % 16) == 0,
-                "p2p_adam_ema_flat_dev_excl: buffers must be 16-byte aligned");
-    const long long hv_lo = (ex_lo + 3) / 4, hv_hi = ex_hi / 4;
-    const long long live = n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
-    long long blocks = (live + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    adam_flat_dev_excl_kernel<true><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(
-        p, g, m, v, n, ex_lo, ex_hi, lr_t_dev, beta1, beta2, eps, gscale, EmaArgs{e, t_dev, decay, warmup});
-    return p2p_check_launch("p2p_adam_ema_flat_dev_excl");
+    const p2p_adam_args a = {p, g, m, v, e, n, ex_lo, ex_hi, lr_t_dev, nullptr, t_dev, nullptr, warmup, 0};
+    return adam_launch(a, {beta1, beta2, eps, 0.f, decay}, gscale, true, "p2p_adam_ema_flat_dev_excl", stream);
 }
 
 // The moving average as a pass of its own, for the steps whose Adam runs in another kernel (p2p_adam_prep_batched): reads the
@@ -260,11 +250,8 @@ __global__ void ema_flat_kernel(const float* __restrict__ p, long long n, EmaArg
 
 extern "C" int p2p_ema_flat(float* e, const float* p, long long n, const int* t_dev, float decay, int warmup, void* stream) {
     P2P_REQUIRE(e && p && n > 0 && t_dev, "p2p_ema_flat: bad args");
-    P2P_REQUIRE(((uintptr_t)e % 16) == 0 && ((uintptr_t)p % 16) == 0, "p2p_ema_flat: buffers must be 16-byte aligned");
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    ema_flat_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(p, n, EmaArgs{e, t_dev, decay, warmup});
+    P2P_REQUIRE(aligned16(e, p), "p2p_ema_flat: buffers must be 16-byte aligned");
+    ema_flat_kernel<<<vector_grid(n / 4), 256, 0, (hipStream_t)stream>>>(p, n, EmaArgs{e, t_dev, decay, warmup});
     return p2p_check_launch("p2p_ema_flat");
 }
 
@@ -381,7 +368,7 @@ extern "C" int p2p_sumsq_partials(const float* g, long long n, long long ex_lo, 
                                   void* stream) {
     P2P_REQUIRE(g && partials && nparts_out && n > 0, "p2p_sumsq_partials: bad args");
     P2P_REQUIRE(0 <= ex_lo && ex_lo <= ex_hi && ex_hi <= n, "p2p_sumsq_partials: the excluded range must lie inside [0, n)");
-    P2P_REQUIRE(((uintptr_t)g % 16) == 0, "p2p_sumsq_partials: the gradient must be 16-byte aligned");
+    P2P_REQUIRE(aligned16(g), "p2p_sumsq_partials: the gradient must be 16-byte aligned");
     const int nb = sumsq_blocks(n);
     sumsq_partials_kernel<<<dim3((unsigned)nb), 256, 0, (hipStream_t)stream>>>(g, n, ex_lo, ex_hi, partials);
     *nparts_out = nb;
@@ -425,94 +412,9 @@ extern "C" int p2p_clip_scale(const float* const* partials, const int* nparts, i
     return p2p_check_launch("p2p_clip_scale");
 }
 
-// p2p_adam_step: adam_flat_dev_excl_kernel's index space (an empty hole leaves every vector live) with the gradient options in
-// front of adam_update.  The clamp and the device scale are exact no-ops when off (g * 1.0f == g), and the element then goes
-// through adam_update / ema_update as in the four entry points this generalises: the same bits.
-struct GradOpts { const float* gscale_dev; float clipvalue; };
-
-__device__ __forceinline__ float grad_clamp(float g, float c) { return c > 0.f ? fminf(fmaxf(g, -c), c) : g; }
-
-template <bool EMA, bool HOLE>
-__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 long long n, long long ex_lo, long long ex_hi, const float* __restrict__ lr_t_dev, float b1, float b2,
-                                 float eps, GradOpts o, EmaArgs ema) {
-    const float lr_t = lr_t_dev[0];
-    const float gscale = o.gscale_dev ? o.gscale_dev[0] : 1.0f;
-    const float c = o.clipvalue;
-    float omb = 0.f;
-    if constexpr (EMA) omb = ema_one_minus_beta(ema);
-    // HOLE = false (ex_lo == ex_hi): adam_flat_dev_kernel's plain index space, and its register footprint -- the early Adam over
-    // the generator's head buckets runs beside the weight-gradient stream's last kernels and must leave them room
-    const long long hv_lo = HOLE ? (ex_lo + 3) / 4 : 0, hv_hi = HOLE ? ex_hi / 4 : 0;
-    const long long hole = hv_hi > hv_lo ? hv_hi - hv_lo : 0;
-    const long long live = n / 4 - hole;
-    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; q < live; q += stride) {
-        const long long i = (!HOLE || q < hv_lo ? q : q + hole) * 4;
-        if (!HOLE || i + 4 <= ex_lo || i >= ex_hi) {
-            f32x4 gi = *(const f32x4*)(g + i), mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float pk = pi[k], mk = mi[k], vk = vi[k];
-                adam_update(pk, grad_clamp(gi[k], c), mk, vk, lr_t, b1, b2, eps, gscale);
-                pi[k] = pk; mi[k] = mk; vi[k] = vk;
-            }
-            *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
-            if constexpr (EMA) {
-                f32x4 ei = *(const f32x4*)(ema.e + i);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float ek = ei[k];
-                    ema_update(ek, pi[k], omb);
-                    ei[k] = ek;
-                }
-                *(f32x4*)(ema.e + i) = ei;
-            }
-        } else {
-            for (long long j = i; j < i + 4; ++j)
-                if (j < ex_lo || j >= ex_hi) {
-                    adam_update(p[j], grad_clamp(g[j], c), m[j], v[j], lr_t, b1, b2, eps, gscale);
-                    if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
-                }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long j = n / 4 * 4; j < n; ++j)
-            if (j < ex_lo || j >= ex_hi) {
-                adam_update(p[j], grad_clamp(g[j], c), m[j], v[j], lr_t, b1, b2, eps, gscale);
-                if constexpr (EMA) ema_update(ema.e[j], p[j], omb);
-            }
-}
-
 extern "C" int p2p_adam_step(const p2p_adam_args* a, void* stream) {
     P2P_REQUIRE(a && a->hyper, "p2p_adam_step: null argument struct");
-    P2P_REQUIRE(a->p && a->g && a->m && a->v && a->n > 0 && a->lr_t_dev, "p2p_adam_step: bad args");
-    P2P_REQUIRE(0 <= a->ex_lo && a->ex_lo <= a->ex_hi && a->ex_hi <= a->n, "p2p_adam_step: the excluded range must lie inside [0, n)");
-    P2P_REQUIRE(!a->e || a->t_dev, "p2p_adam_step: the moving average needs t_dev");
-    P2P_REQUIRE(((uintptr_t)a->p % 16) == 0 && ((uintptr_t)a->g % 16) == 0 && ((uintptr_t)a->m % 16) == 0 &&
-                    ((uintptr_t)a->v % 16) == 0 && ((uintptr_t)a->e % 16) == 0,
-                "p2p_adam_step: buffers must be 16-byte aligned");
-    const p2p_adam_hyper h = *a->hyper;
-    const long long hv_lo = (a->ex_lo + 3) / 4, hv_hi = a->ex_hi / 4;
-    const long long live = a->n / 4 - (hv_hi > hv_lo ? hv_hi - hv_lo : 0);
-    long long blocks = (live + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    const GradOpts o = {a->gscale_dev, h.clipvalue};
-    const EmaArgs ema = a->e ? EmaArgs{a->e, a->t_dev, h.ema_decay, a->ema_warmup} : EmaArgs{nullptr, nullptr, 0.f, 0};
-    const dim3 grid((unsigned)blocks);
-    const hipStream_t st = (hipStream_t)stream;
-#define ADAM_STEP_LAUNCH(EMA, HOLE)                                                                                                \
-    adam_step_kernel<EMA, HOLE><<<grid, 256, 0, st>>>(a->p, a->g, a->m, a->v, a->n, a->ex_lo, a->ex_hi, a->lr_t_dev, h.beta1, h.beta2, \
-                                                      h.eps, o, ema)
-    const bool holed = a->ex_hi > a->ex_lo;
-    if (a->e && holed) ADAM_STEP_LAUNCH(true, true);
-    else if (a->e) ADAM_STEP_LAUNCH(true, false);
-    else if (holed) ADAM_STEP_LAUNCH(false, true);
-    else ADAM_STEP_LAUNCH(false, false);
-#undef ADAM_STEP_LAUNCH
-    return p2p_check_launch("p2p_adam_step");
+    return adam_launch(*a, *a->hyper, 1.0f, a->e != nullptr, "p2p_adam_step", stream);
 }
 
 __global__ void counter_add_kernel(long long* c, long long inc) { c[0] += inc; }
@@ -544,11 +446,8 @@ __global__ void grad_accumulate_kernel(float* __restrict__ dst, const float* __r
 
 extern "C" int p2p_grad_accumulate(float* dst, const float* src, long long n, int first, void* stream) {
     P2P_REQUIRE(dst && src && n > 0, "p2p_grad_accumulate: bad args");
-    P2P_REQUIRE(((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0, "p2p_grad_accumulate: buffers must be 16-byte aligned");
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    grad_accumulate_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(dst, src, n, first);
+    P2P_REQUIRE(aligned16(dst, src), "p2p_grad_accumulate: buffers must be 16-byte aligned");
+    grad_accumulate_kernel<<<vector_grid(n / 4), 256, 0, (hipStream_t)stream>>>(dst, src, n, first);
     return p2p_check_launch("p2p_grad_accumulate");
 }
 
@@ -645,8 +544,9 @@ __global__ void weight_prep_batched_kernel(const p2p_prep_task* __restrict__ tas
 
 // ---- Adam + weight copies in one pass (SURVEY.md 2.3 K18 "also emits the bf16 weight copy") -------------------------------
 // The same tiling as the batched weight prep, but the master tile is UPDATED on the way: theta, g, m, v are read, the Keras
-// Adam step of adam_flat_dev_kernel is applied (same expressions: bit-identical results), theta, m, v are written back and the
-// fresh value goes straight into the two operand copies.  Saves the second read of the 117 MB master.  Every master element
+// Adam step of p2p_adam_flat_dev is applied (the same expressions, but written out in ADAM_ONE and contracted as the compiler sees
+// fit, not adam_update's spelled-out roundings: the masters may differ from the flat pass in the last bit, which is what
+// tests/test_train_step_gpu.py allows this pair), theta, m, v are written back and the fresh value goes straight into the two operand copies.  Saves the second read of the 117 MB master.  Every master element
 // lies in exactly one tile of its task; the caller lists every kernel ONCE.
 struct AdamCtx { float* p0; const float* g0; float* m0; float* v0; const float* lr_t; float b1, b2, eps; };
 
@@ -738,8 +638,7 @@ extern "C" int p2p_adam_prep_batched(int dtype, long long n_elems, const p2p_pre
     P2P_REQUIRE(tasks_dev && ntasks >= 1 && ntasks <= 64 && total_blocks >= 1 && total_blocks < (1LL << 31) && n_elems > 0,
                 "p2p_adam_prep_batched: bad args");
     P2P_REQUIRE(params && grads && m && v && lr_t_dev, "p2p_adam_prep_batched: null pointer");
-    P2P_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-                "p2p_adam_prep_batched: buffers must be 16-byte aligned");
+    P2P_REQUIRE(aligned16(params, grads, m, v), "p2p_adam_prep_batched: buffers must be 16-byte aligned");
     AdamCtx c = {params, grads, m, v, lr_t_dev, beta1, beta2, eps};
     P2P_DISPATCH_DTYPE(dtype, (adam_prep_batched_kernel<T><<<dim3((unsigned)total_blocks), 256, 0, (hipStream_t)stream>>>(tasks_dev, ntasks, c)));
     return p2p_check_launch("p2p_adam_prep_batched");

@@ -199,7 +199,8 @@ def _adam_state(n, seed):
 
 
 def _run_adam(entry, state, hole, ema, t=3, lr_t=1.7e-4, gscale=None, clipvalue=0.0, decay=0.99, warmup=1):
-    """one launch of `entry` ("step" or one of the four flat entry points) on fresh guarded copies: (p, m, v, e) after"""
+    """one launch of `entry` ("step" or one of the four flat entry points) on fresh guarded copies: (p, m, v, e) after; `gscale`
+    reaches "step" as a device scalar and a flat entry point by value"""
     p, g, m, v, e = state
     n = p.size
     bufs = [_guarded(x) for x in (p, g, m, v, e)]
@@ -215,7 +216,7 @@ def _run_adam(entry, state, hole, ema, t=3, lr_t=1.7e-4, gscale=None, clipvalue=
         L.call("p2p_adam_step", C.byref(a), _stream())
     else:
         name = "p2p_adam" + ("_ema" if ema else "") + "_flat_dev" + ("_excl" if hole else "")
-        args = ptr[:4] + ([ptr[4]] if ema else []) + [n] + ([lo, hi] if hole else []) + [lrp, B1, B2, EPS, 1.0]
+        args = ptr[:4] + ([ptr[4]] if ema else []) + [n] + ([lo, hi] if hole else []) + [lrp, B1, B2, EPS, 1.0 if gscale is None else gscale]
         args += [tp, decay, warmup] if ema else []
         L.call(name, *args, _stream())
     torch.cuda.synchronize()
@@ -289,6 +290,54 @@ def test_adam_step_gradient_options_equal_the_restatement(n, hole):
     if hole:
         live[hole[0]:hole[1]] = False
     assert np.isnan(got[0][live]).all() and _same(got[0][~live], p[~live])
+
+
+# One whole sweep of the capped grid (8192 workgroups of 256 lanes, one 16-byte vector each), one more workgroup's worth of vectors
+# and a 3-element tail: the lanes of the first workgroup walk on to a second vector, everyone else stops after one.  The holes take
+# out fewer than 256 vectors, so the grid stays capped and the second sweep is still there.
+ADAM_SWEEP = 8192 * 256 * 4
+ADAM_N = ADAM_SWEEP + 4 * 256 + 3
+ADAM_SWEEP_HOLES = {"no_hole": None,
+                    "across_the_sweep": (ADAM_SWEEP - 100, ADAM_SWEEP + 200),         # whole vectors on both sides of the boundary
+                    "unaligned_ends": (1001, 1502)}                                   # cuts a vector at either end
+SWEEP_SCALE = 0.37
+
+
+@pytest.fixture(scope="module")
+def sweep_case():
+    """the state, the clip threshold and the restatement's (p, m, v) without a hole for the three gradient forms, computed once"""
+    state = _adam_state(ADAM_N, 7)
+    p, g, m, v, e = state
+    c = float(np.median(np.abs(g)))
+    want = {"plain": OO.adam_flat(p, g, m, v, 1.7e-4, B1, B2, EPS),
+            "clipvalue": OO.adam_flat(p, g, m, v, 1.7e-4, B1, B2, EPS, clipvalue=c),
+            "scale": OO.adam_flat(p, g, m, v, 1.7e-4, B1, B2, EPS, gscale=SWEEP_SCALE)}
+    for a in state + tuple(x for w in want.values() for x in w):
+        a.setflags(write=False)
+    return state, c, want
+
+
+@pytest.mark.parametrize("hole", list(ADAM_SWEEP_HOLES))
+def test_adam_past_one_sweep_of_the_capped_grid(sweep_case, hole):
+    """every flat entry point (scale 1, and a scale by value) and p2p_adam_step (clipvalue with the average, a device scale
+    without) at an n the capped grid covers in two sweeps: the restatement's bits outside the hole, the hole and the guards
+    untouched"""
+    state, c, want = sweep_case
+    ex = ADAM_SWEEP_HOLES[hole]
+    live = np.ones(ADAM_N, bool)
+    if ex:
+        live[ex[0]:ex[1]] = False
+    assert ADAM_N // 4 - (~live).sum() // 4 > ADAM_SWEEP // 4           # more live vectors than lanes in the capped grid
+    runs = [("flat", "plain", False, {}), ("flat", "plain", True, {}),
+            ("step", "clipvalue", True, {"clipvalue": c}), ("step", "scale", False, {"gscale": SWEEP_SCALE}),
+            ("flat", "scale", False, {"gscale": SWEEP_SCALE})]
+    for entry, form, ema, opts in runs:
+        got = _run_adam(entry, state, ex, ema, **opts)
+        wp, wm, wv = want[form]
+        we = OO.ema_element(state[4], wp, 3, 0.99, 1) if ema else state[4]
+        for name, new, restated, before in zip("pmve", got, (wp, wm, wv, we), (state[0], state[2], state[3], state[4])):
+            assert _same(new[live], restated[live]), (entry, form, ema, name)
+            assert _same(new[~live], before[~live]), (entry, form, ema, name, "the hole was written")
 
 
 # ---------------------------------------------------------------------------------------------------------------- engine

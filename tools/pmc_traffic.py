@@ -9,6 +9,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 from collections import defaultdict
 
@@ -20,7 +21,7 @@ FAMILIES = {"igemm_pipe_kernel": ("p2p_igemm", True), "igemm_kernel": ("p2p_igem
             "norm_act_fwd_vec": ("p2p_norm_act_fwd", True), "norm_act_fwd_small": ("p2p_norm_act_fwd", True),
             "norm_act_bwd_vec": ("p2p_norm_act_bwd", True), "norm_act_bwd_small": ("p2p_norm_act_bwd", True),
             "norm_act_fwd_reg": ("p2p_norm_act_fwd", True), "norm_act_bwd_reg": ("p2p_norm_act_bwd", True),
-            "adam_flat_dev_kernel": ("p2p_adam_flat_dev", True),
+            "adam_kernel": ("p2p_adam_flat_dev", True), "adam_flat_dev_kernel": ("p2p_adam_flat_dev", True),   # the second: older profiles
             "weight_prep_kernel": ("p2p_weight_prep_pad", True), "rgbuv_hist_fwd_kernel": ("p2p_rgbuv_hist_fwd", True),
             "rgbuv_hist_bwd_kernel": ("p2p_rgbuv_hist_hellinger_bwd", True), "rgbuv_hist_fwd3_kernel": ("p2p_rgbuv_hist_fwd3", True),
             "rgbuv_hist_fold_kernel": ("p2p_rgbuv_hist_fwd3", False),
@@ -49,6 +50,9 @@ def load(folder, counter):
                 # GEN (edge) instantiations of igemm_kernel are a different entry point
                 if fam == "p2p_igemm" and "igemm_kernel" in name and ("Lb1ELb" in name or ", true," in name):
                     fam = "p2p_igemm_edge"
+                # adam_kernel<EMA, HOLE, OPTS> serves every flat Adam entry point: the forms with a hole are kept apart
+                if "adam_kernel" in name and re.search(r"adam_kernel(ILb[01]ELb1E|<\w+, true,)", name):
+                    fam = "p2p_adam_flat_dev_excl"
                 per[fam][0] += float(row["Counter_Value"])
                 per[fam][1] += 1 if primary else 0
     return per
