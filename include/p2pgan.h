@@ -613,7 +613,9 @@ int p2p_diffaug_bwd(int N, int H, int W, const float* grad_out, const float* col
  * dz = grad_scale * (softmax(z) - onehot(target)) and the f32 probabilities; loss_out[0] = inv_count * sum CCE with
  * CCE = log(sum_c exp(z_c - max)) - (z_target - max) (the logits form Keras 2.9 uses for a softmax-activated output,
  * finite for every input), loss_out[1] = inv_count / C * sum |onehot - p|.  loss_part: workspace of
- * 2 * P2P_SOFTMAX_MAX_BLOCKS floats (one partial per workgroup, summed in workgroup order: bit-reproducible). */
+ * 2 * P2P_SOFTMAX_MAX_BLOCKS floats (one partial per workgroup, summed in workgroup order: bit-reproducible).
+ * 1 <= C <= 512 in f32, 1 <= C <= 256 in bf16: the indices travel as values of `dtype`, and indices above 256 are not bf16
+ * values (257 would be read and stored as 256).  Anything else returns a negative code and sets p2p_last_error before any launch. */
 #define P2P_SOFTMAX_MAX_BLOCKS 8192
 int p2p_softmax_cce_argmax(int dtype, int N, int H, int W, int C, const p2p_tensor* z, const p2p_tensor* target,
                            const p2p_tensor* fake_idx, float grad_scale, float inv_count, const p2p_tensor* dz,

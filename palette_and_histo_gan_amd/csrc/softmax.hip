@@ -292,6 +292,8 @@ extern "C" int p2p_softmax_cce_argmax(int dtype, int N, int H, int W, int C, con
                                       const p2p_tensor* fake_idx, float grad_scale, float inv_count, const p2p_tensor* dz,
                                       float* probs_out, float* loss_part, float* loss_out, void* stream) {
     P2P_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C <= 512, "p2p_softmax_cce_argmax: bad shape (C <= 512)");
+    // target and fake_idx carry indices as values of `dtype`: bf16 has 8 significant bits, so 257, 259, ... are no bf16 values
+    P2P_REQUIRE(dtype != P2P_BF16 || C <= 256, "p2p_softmax_cce_argmax: C = %d in bf16: indices above 256 are not bf16 values (C <= 256, or f32)", C);
     P2P_REQUIRE(z && z->ptr && target && target->ptr && fake_idx && fake_idx->ptr && loss_out && loss_part, "p2p_softmax_cce_argmax: null pointer");
     hipStream_t st = (hipStream_t)stream;
     TView d;

@@ -225,6 +225,18 @@ def test_head_dgrad_exact(n):
     _run("p2p_head_dgrad", [BF, n, S, S, cd, 32, R._vd(S, S, cd, halo=R.HALO), PTR, E.up32(cg), R._vd(S, S, 40), None], seed=70 + n)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("h", [8, 16])
+def test_head_dgrad_exact_short_images(h, n):
+    """p2p_head_dgrad accepts any H % 8 == 0 at W = 64.  H = 8: the one workgroup of an image has the top and the bottom halo in
+    its 11-row strip at once; H = 16: one halo each; n = 3: image boundaries between workgroups.  The output pixels have 40
+    channels: the 8 behind the 32 written ones hold the checker's sentinel, which must survive (OutBuf.check_around)."""
+    S, cg, cd = 64, 33, 256
+    assert L.lib().p2p_head_dgrad_ok(BF, n, h, S, cd, 32, E.up32(cg), cd, 40)
+    print()
+    _run("p2p_head_dgrad", [BF, n, h, S, cd, 32, R._vd(h, S, cd, halo=R.HALO), PTR, E.up32(cg), R._vd(h, S, 40), None], seed=170 + h + n)
+
+
 def test_column_sums_exact():
     """p2p_colsum (a power-of-two scale) and p2p_colsum_batched over ragged tasks inside a larger output buffer"""
     print()
